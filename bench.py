@@ -1,6 +1,6 @@
 """Headline benchmark: captions/s of the Patch-ioner hot path on MI355X (BASELINE.json config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work for N > 1: started without a torch.distributed.run environment, ``bench.py --gpus N`` spawns its N ranks
@@ -27,9 +27,6 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 # +1.2 % captions/s through the pipeline on one box, two alternations (8.58 against 8.47 k), nothing on the synchronous forward.
 # The same default as patchioner_amd/__init__.py and tests/conftest.py; the effective value is reported in `config.env`.
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
-# Eight hardware queues instead of HIP's four: the pipeline runs five streams side by side (caller, stage 1, three decodes), and whether two of them
-# shared a queue depended on creation order and on a timing probe (patchioner_amd/__init__.py); same throughput when nothing is aliased.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import torch  # noqa: E402
 
@@ -67,6 +64,21 @@ def make_inputs():
     rng = np.random.RandomState(2)
     traces = [gc.block_trace(int(rng.randint(0, 13)), int(rng.randint(0, 13))) for _ in range(BATCH)]
     return imgs, traces
+
+
+def dump_outputs(path: str, outs, ids) -> None:
+    """What the timed path handed its caller in its last step, as float32 .npy files: `trace_ids` (BATCH x 30 greedy token ids, exact
+    in float32) and `trace_capts` (the caption strings as Unicode code points, one row per caption, padded with -1).  The inputs are
+    seeded, so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "trace_ids.npy"), ids.numpy().astype(np.float32))
+    caps = outs["trace_capts"]
+    width = max([len(c) for c in caps] + [1])
+    cp = np.full((len(caps), width), -1, dtype=np.float32)
+    for i, c in enumerate(caps):
+        cp[i, :len(c)] = [ord(ch) for ch in c]
+    np.save(os.path.join(path, "trace_capts.npy"), cp)
 
 
 def _stats(xs):
@@ -327,6 +339,8 @@ def main():
                     help="mode=group: decoders (the model's own + clones on the same weights, each with its own workspace and stream) that consecutive groups' decodes alternate over")
     ap.add_argument("--vit-batches", type=int, default=int(os.environ.get("PIO_BENCH_VIT_BATCHES", "5")),
                     help="mode=group: consecutive bs-16 batches that share one ViT launch (1 = a launch per batch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (token ids, captions) to DIR/<name>.npy as float32")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:     # the driver's plain `python bench.py --gpus N`
@@ -421,6 +435,8 @@ def main():
     outs, ids = run_steps(args.steps)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:        # copied now: the later regions reuse the decode buffers that `ids` lives in
+        dump_outputs(args.dump_outputs, outs, ids.cpu())
     # Per-group statistics of the pipelined path over >= 100 groups (median + p95), outside the K timed steps:
     # the interval between consecutive groups' ids becoming available on the host.
     group_ms = []
@@ -628,7 +644,7 @@ def main():
                                    "talk2dino_decap_COCO, ViT-B/14-reg 224^2, batch 16/GPU, caption_from=patches "
                                    "(one 16-patch trace region per image), bank 591753x768 fp32, 30-step greedy decode; `value` is measured "
                                    "through the throughput API (value_api), the drop-in forward() figure is forward_sync",
-                       "env": {"HIP_FORCE_DEV_KERNARG": os.environ.get("HIP_FORCE_DEV_KERNARG"), "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")},
+                       "env": {"HIP_FORCE_DEV_KERNARG": os.environ.get("HIP_FORCE_DEV_KERNARG")},
                        "arithmetic": {"vit": "fp16 operands, fp32 accumulation (v_mfma_f32_32x32x16_f16), fp32 residual stream / LayerNorm",
                                       "projection": "operands as fp16 hi + lo pairs (22 significant bits) on v_mfma_f32_16x16x32_f16, fp32 "
                                                     "accumulation and soft-max; as close to fp64 as an fp32 evaluation (DESIGN.md section 3)",

@@ -28,8 +28,6 @@ from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
-import patchioner_amd as _pkg
-
 
 # CU-masked streams (pio_stream_create) live for the life of the PROCESS, like torch's own pooled streams: torch's caching
 # allocators -- device blocks with record_stream'ed uses, pinned host blocks used by a non-blocking copy -- keep the raw
@@ -115,9 +113,9 @@ class TraceCaptionPipeline:
         # kernels find idle CUs instead of queueing behind resident GEMM workgroups (None / 0: no restriction).
         self._raw_streams = []
         # Stage 1 runs on a HIGH-PRIORITY stream -- not for the priority: HIP maps the streams of one priority class round-robin onto
-        # GPU_MAX_HW_QUEUES = 4 hardware queues, and with one stage stream, three decode streams and the caller's stream two of them
+        # its 4 hardware queues (the runtime's default), and with one stage stream, three decode streams and the caller's stream two of them
         # SHARED a queue, i.e. one decode chain ran serialised with the ViT launches instead of beside them.  A stream of another
-        # priority class gets a queue of its own: 8.62 against 7.95 k captions/s on one box (the same with GPU_MAX_HW_QUEUES=8
+        # priority class gets a queue of its own: 8.62 against 7.95 k captions/s on one box (the same with eight hardware queues
         # and default priorities; decode streams high and stage normal: 8.52 k; both high: 8.57 k).
         self.stage_streams = [self._make_stream(stage_cus, priority=int(os.environ.get("PIO_STAGE_PRIO", "-1"))) for _ in self.stage_models]
         # ... and the decode to the LAST `decode_cus` compute units (a true partition when stage_cus + decode_cus <= total)
@@ -135,7 +133,7 @@ class TraceCaptionPipeline:
 
     def _concurrent_streams(self, n: int, priority: int = 0, candidates: int = 16, beside: Sequence = ()) -> List[torch.cuda.Stream]:
         """``n`` streams that the device really runs side by side.  HIP deals the streams of a priority class round-robin onto
-        its few hardware queues (GPU_MAX_HW_QUEUES, default 4) in creation order -- the caller's, torch's and this library's own
+        its few hardware queues (4 by default) in creation order -- the caller's, torch's and this library's own
         included -- and two streams that share a queue run one after the other: whether three decode streams overlap depended
         on what had been created before them (BASELINE config 3 through RegionCaptionPipeline: 6.8 or 10.3 k box captions/s for
         the same settings).  So candidates are taken from torch's pool and PROBED: a spin kernel on each stream of the set at
@@ -181,10 +179,7 @@ class TraceCaptionPipeline:
             import sys
             print("patchioner_amd.pipeline: %d of %d decode streams run beside the stage stream(s); %d share a hardware queue "
                   "(probe ratios %s, one spin %.3f ms)%s" % (len(chosen), n, max(0, n - len(chosen)), ratios, base * 1e3,
-                  "" if len(chosen) == n else " -- use fewer decode clones, or start the process with GPU_MAX_HW_QUEUES=8 (HIP reads it "
-                  "once, at its first GPU call: %s)" % ("this process had initialised the GPU before patchioner_amd was imported, so the "
-                                                        "package's default of 8 came too late" if _pkg._HIP_UP_AT_IMPORT else
-                                                        "effective value here: %s" % os.environ.get("GPU_MAX_HW_QUEUES"))), file=sys.stderr)
+                  "" if len(chosen) == n else " -- use fewer decode clones"), file=sys.stderr)
         return chosen + spare[:n - len(chosen)]               # not enough independent queues: take what there is
 
     def _make_stream(self, n_cus, from_top: bool = False, priority: int = 0):

@@ -29,3 +29,19 @@ def test_bench_gpus_2_launches_its_own_ranks():
 def test_bench_self_launch_propagates_a_failing_rank():
     r = _run({"PIO_BENCH_DRY_FAIL": "1"}, "--gpus", "2", "--steps", "1", "--warmup", "0")
     assert r.returncode != 0
+
+
+def test_dump_outputs_writes_ids_and_captions_as_float32(tmp_path):
+    """--dump-outputs DIR: the last step's token ids and captions, float32 .npy files that decode back to exactly what the caller got."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    ids = torch.arange(16 * 30, dtype=torch.int32).view(16, 30) * 97
+    caps = ["a dog on a bench", "", "café au lait"] + ["x" * (i + 1) for i in range(13)]
+    bench.dump_outputs(str(tmp_path / "out"), {"trace_capts": caps}, ids)
+    got_ids = np.load(tmp_path / "out" / "trace_ids.npy")
+    got_caps = np.load(tmp_path / "out" / "trace_capts.npy")
+    assert got_ids.dtype == np.float32 and got_caps.dtype == np.float32
+    assert np.array_equal(got_ids, ids.numpy().astype(np.float32))
+    assert ["".join(chr(int(v)) for v in row if v >= 0) for row in got_caps] == caps
