@@ -299,6 +299,36 @@ int pio_ctx_clean(pio_handle h, const float* dirty, const float* ctx, int32_t R,
 int pio_preprocess(pio_handle h, const void* pixels, const int64_t* offsets, const int32_t* wh, int32_t B,
                    int32_t resize_dim, int32_t crop_dim, int32_t mode, float* out, void* stream);
 
+/* ---- CLIP text tower (clip.model.CLIP.encode_text; the memory-bank build P/src/decap/im2txtprojection/
+ *      im2txtprojection.py:511-524, 650-657 and Patchioner's online_texts, :491-493).  A handle of its own: a text-only
+ *      encoder needs no ViT, and pio_config is unchanged.
+ *      Weights use the checkpoint's own names: token_embedding.weight [V,W], positional_embedding [ctx,W],
+ *      transformer.resblocks.{i}.{ln_1,ln_2}.{weight,bias}, .attn.in_proj_weight [3W,W], .attn.in_proj_bias,
+ *      .attn.out_proj.{weight,bias}, .mlp.c_fc.{weight,bias} [4W,W], .mlp.c_proj.{weight,bias} [W,4W],
+ *      ln_final.{weight,bias}, text_projection [W,embed_dim].  Other keys are refused (PIO_ERR_UNKNOWN_WEIGHT).
+ *      All workspaces are allocated by pio_text_finalize; pio_text_encode allocates nothing. */
+typedef struct pio_text_context* pio_text_handle;
+typedef struct {
+  int32_t device;             /* HIP device ordinal */
+  int32_t width;              /* 512 (ViT-B/16, B/32) or 768 (ViT-L/14) */
+  int32_t layers;             /* 12 */
+  int32_t heads;              /* width / 64 */
+  int32_t context_length;     /* 77 (<= 120) */
+  int32_t vocab_size;         /* 49408 */
+  int32_t embed_dim;          /* width of text_projection's output (512 / 768) */
+  int32_t max_texts;          /* captions per pio_text_encode call */
+  int32_t operand_type;       /* 0 = fp16 MFMA operands (fp32 accumulate, fp32 residual stream); 2 = exact fp32 (parity mode) */
+} pio_text_config;
+
+int pio_text_create(const pio_text_config* cfg, pio_text_handle* out);
+int pio_text_destroy(pio_text_handle h);
+int pio_text_load_weight(pio_text_handle h, const char* key, const float* host, const int64_t* shape, int32_t ndim);
+int pio_text_finalize(pio_text_handle h);
+/* ids_dev [N,L] int32 on the device (clip.tokenize rows: SOT ... EOT, zero padded; L <= context_length, any L >= 1);
+ * out_dev [N,embed_dim] fp32 = ln_final(x[n, argmax ids[n]]) @ text_projection.  A caption's row has the same bits whatever N
+ * and L hold it.  Synchronises the stream at the end (to report an id outside the vocabulary: PIO_ERR_INVALID_ARG). */
+int pio_text_encode(pio_text_handle h, const int32_t* ids_dev, int32_t N, int32_t L, float* out_dev, pio_stream stream);
+
 /* Introspection used by the host mirror and the tests. */
 int pio_num_tokens(pio_handle h);     /* T */
 int pio_grid_side(pio_handle h);      /* n */

@@ -38,6 +38,13 @@ class PioConfig(ctypes.Structure):
     ]
 
 
+class PioTextConfig(ctypes.Structure):
+    _fields_ = [
+        ("device", c_int32), ("width", c_int32), ("layers", c_int32), ("heads", c_int32), ("context_length", c_int32),
+        ("vocab_size", c_int32), ("embed_dim", c_int32), ("max_texts", c_int32), ("operand_type", c_int32),
+    ]
+
+
 # every symbol include/patchioner_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "pio_last_error": (c_char_p, []),
@@ -85,6 +92,11 @@ SIGNATURES = {
                                 c_void_p]),
     "pio_preprocess": (c_int32, [c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int32), c_int32, c_int32, c_int32, c_int32,
                                  c_void_p, c_void_p]),
+    "pio_text_create": (c_int32, [POINTER(PioTextConfig), POINTER(c_void_p)]),
+    "pio_text_destroy": (c_int32, [c_void_p]),
+    "pio_text_load_weight": (c_int32, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int32]),
+    "pio_text_finalize": (c_int32, [c_void_p]),
+    "pio_text_encode": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "pio_num_tokens": (c_int32, [c_void_p]),
     "pio_grid_side": (c_int32, [c_void_p]),
     "pio_bank_rows": (c_int64, [c_void_p]),

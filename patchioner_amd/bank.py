@@ -3,9 +3,10 @@ im2txtprojection.py:448-560): captions -> CLIP text features -> Talk2DINO's text
 ``<name>-text`` in an HDF5 file whose name encodes the configuration (:100-170, :234).
 
 What runs where:
-  * the CLIP text tower is NOT part of this package (bank build needs CLIP + the caption datasets); the
-    caller hands in ``encode_text(list of str) -> [n, clip_dim] float tensor`` -- ``lambda t: clip_model.encode_text(
-    clip.tokenize(t))`` in the reference's terms (:519-520);
+  * the CLIP text tower: with ``encode_text=None`` the package's own (clip_text.ClipTextEncoder: host BPE, the tower on the
+    MI355X, csrc/text_encoder.hip), from ``clip_text_weights`` / ~/.cache/clip / ``synthetic_seed``; the features stay on the
+    device through the Talk2DINO projection.  A caller may still hand in ``encode_text(list of str) -> [n, clip_dim]`` --
+    ``lambda t: clip_model.encode_text(clip.tokenize(t))`` in the reference's terms (:519-520);
   * ``project_clip_txt`` (talk2dino.py:73-83) runs on the MI355X through ``pio_text_project`` (exact fp32 MFMA GEMMs);
   * the file is written by ``h5lite.write_bank`` (no h5py on the image) in the layout h5py gives the reference's
     ``create_dataset`` calls, and read back by ``h5lite.read_datasets`` / ``Patchioner(memory_bank=...)``.
@@ -59,12 +60,17 @@ def filename_components(projection_type="coco_captions", use_talk2dino=True, lin
     return prefix, dataset_name, attn, postfix
 
 
+def default_clip_model(use_talk2dino=True) -> str:
+    """The reference's default CLIP model (:289-299): ViT-B/16 with Talk2DINO, ViT-B/32 without."""
+    return "ViT-B/16" if use_talk2dino else "ViT-B/32"
+
+
 def memory_bank_filename(projection_type="coco_captions", clip_modelname=None, support_memory_size=591753, use_talk2dino=True,
                          **kw) -> Tuple[str, str]:
     """-> (file name, dataset name).  ``{prefix}{dataset}_text_embeddings{attn}{postfix}-{clip model, / -> .}-{size}.h5`` (:234);
     the default CLIP model is ViT-B/16 with Talk2DINO and ViT-B/32 without (:289-299)."""
     if clip_modelname is None:
-        clip_modelname = "ViT-B/16" if use_talk2dino else "ViT-B/32"
+        clip_modelname = default_clip_model(use_talk2dino)
     prefix, dataset_name, attn, postfix = filename_components(projection_type, use_talk2dino, **kw)
     return (prefix + "%s_text_embeddings%s%s-%s-%d.h5" % (dataset_name, attn, postfix, clip_modelname.replace("/", "."),
                                                           support_memory_size), dataset_name)
@@ -84,13 +90,26 @@ def talk2dino_text_weights(state_dict) -> dict:
             "b2": sd["hidden_layers.0.bias"].float() if "hidden_layers.0.bias" in sd else None}
 
 
-def build_memory_bank(engine, texts: Sequence[str], encode_text: Callable[[List[str]], torch.Tensor], out_dir: str,
+def build_memory_bank(engine, texts: Sequence[str], encode_text: Optional[Callable[[List[str]], torch.Tensor]], out_dir: str,
                       projection_type="coco_captions", clip_modelname=None, support_memory_size: Optional[int] = None,
-                      talk2dino_state_dict=None, act="tanh", batch_size: int = 1000, **name_kw) -> str:
+                      talk2dino_state_dict=None, act="tanh", batch_size: int = 1000, clip_text_weights=None,
+                      synthetic_seed: Optional[int] = None, clip_text_dtype: str = "fp16", **name_kw) -> str:
     """``_build_support_memory`` (:448-560) for a list of captions.  ``talk2dino_state_dict`` None = a plain CLIP bank
-    (use_talk2dino False).  Returns the path of the .h5 written into ``out_dir``."""
+    (use_talk2dino False).  ``encode_text`` None: the device text tower of ``clip_modelname`` (default: ViT-B/16 with
+    Talk2DINO, ViT-B/32 without), weights from ``clip_text_weights``, ~/.cache/clip or ``synthetic_seed``
+    (clip_text.resolve_text_weights), operands ``clip_text_dtype``; its device memory is freed before this returns.
+    Returns the path of the .h5 written into ``out_dir``."""
     texts = list(texts)
     use_t2d = talk2dino_state_dict is not None
+    if encode_text is None:
+        from .clip_text import ClipTextEncoder
+        enc = ClipTextEncoder(clip_modelname or default_clip_model(use_t2d), weights=clip_text_weights, synthetic_seed=synthetic_seed,
+                              operand_type=clip_text_dtype, device=engine.device, max_texts=min(max(batch_size, 1), 1024))
+        try:
+            return build_memory_bank(engine, texts, enc.encode_text, out_dir, projection_type, clip_modelname, support_memory_size,
+                                     talk2dino_state_dict, act, batch_size, **name_kw)
+        finally:
+            enc.close()
     size = len(texts) if support_memory_size is None else int(support_memory_size)
     if len(texts) > size:
         raise ValueError("%d texts do not fit a support memory of %d rows" % (len(texts), size))

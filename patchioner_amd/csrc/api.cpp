@@ -28,6 +28,15 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
+}  // namespace
+
+// the other translation units of the C ABI (text_api.cpp) report through the same per-thread message
+namespace pio {
+int api_fail(int code, const std::string& msg) { return fail(code, msg); }
+}  // namespace pio
+
+namespace {
+
 #define HIP_OK(expr)                                                                              \
   do {                                                                                            \
     hipError_t _e = (expr);                                                                       \

@@ -97,6 +97,17 @@ hipError_t launch_attention_f32(const float* qkv, int B, int H, int T, int Tp, i
 hipError_t launch_resid_ls_f32(float* x, const float* y, const float* ls, size_t total, int D, hipStream_t s);
 hipError_t launch_gelu_f32(float* y, size_t n, int act, hipStream_t s);
 hipError_t launch_layernorm_f32(const float* x, const float* w, const float* b, float eps, int M, int D, float* y, hipStream_t s);
+// ---- text_encoder.hip: the OpenAI-CLIP text tower (causal; caption s = rows [s Tp, s Tp + Tp), Tp = round_up(L, 8))
+// x[s Tp + t] = tok[ids[s][t]] + pos[t] for t < L, zero rows t >= L; an id outside [0, V) gives a zero row and sets *err
+hipError_t launch_text_embed(const int32_t* ids, int N, int L, int Tp, int V, int W, const float* tok, const float* pos, float* x,
+                             int32_t* err, hipStream_t s);
+// causal attention on MFMA, one workgroup per (caption, head): a.B = captions, a.T unused, round_up(a.Tp, 32) <= min(a.Tk, 128)
+hipError_t launch_text_attention(OperandType t, const VitAttnArgs& a, hipStream_t s);
+// the same in plain fp32 (parity mode): qkv [N*Tp][3D] -> out [N*Tp][D]
+hipError_t launch_text_attention_f32(const float* qkv, int N, int H, int Tp, int D, float scale, float* out, hipStream_t s);
+// out[s] = LayerNorm(x[s Tp + first argmax of ids[s]]) @ proj  (proj [W][E]; fp32)
+hipError_t launch_text_pool(const float* x, const int32_t* ids, int N, int L, int Tp, int W, int E, const float* lw, const float* lb,
+                            float eps, const float* proj, float* out, hipStream_t s);
 
 // imgs [B][3][S][S] fp32 -> patch rows [B*n2][Kpad] (k = c*p*p + py*p + px; columns >= 3*p*p stay zero)
 hipError_t launch_im2col(OperandType t, const float* imgs, int B, int S, int p, int n, int Kpad, void* out,

@@ -15,6 +15,13 @@ Build-specific config keys (there is no network on the target, so nothing is fet
   memory_bank      path (.npy / .pt / .h5) or tensor [M, D] of the text memory bank
   synthetic_seed   int: synthesise any weights / bank not given (seeded; see weights.py)
   max_batch, max_prefixes, vit_dtype ("fp16" | "bf16")
+  clip_text_weights  path (clip.load JIT archive or state dict) or dict of the CLIP text tower that encodes
+                   ``online_texts`` (clip_text.py).  Order of the sources: this key, ~/.cache/clip/<name>.pt (where clip.load
+                   puts it), synthetic_seed, else FileNotFoundError
+  clip_text_dtype  "fp16" (default) | "fp32": operands of that text tower (fp32 = the exact parity mode)
+  talk2dino_projection_weights  path or dict of the Talk2DINO ProjectionLayer that maps the online_texts features into the
+                   DINOv2 space (use_talk2dino_project).  Order: this key, talk2dino_weights, synthetic_seed, else
+                   FileNotFoundError
 """
 from __future__ import annotations
 
@@ -85,7 +92,8 @@ class Patchioner(nn.Module):
                  use_open_clip=False, viecap_config=None, regionclip_config=None, invite_config=None,
                  denseclip_config=None, alphaclip_config=None, clipcap_config=None, hf_repo_id=None,
                  dino_weights=None, memory_bank=None, synthetic_seed=None, max_batch=16, max_prefixes=128,
-                 vit_dtype="fp16", memory_bank_texts=None, **kwargs):
+                 vit_dtype="fp16", memory_bank_texts=None, clip_text_weights=None, clip_text_dtype="fp16",
+                 talk2dino_projection_weights=None, **kwargs):
         super().__init__(**kwargs)
         given = dict(proxyclip_clipmodel=proxyclip_clipmodel,
                      regionclip_config=regionclip_config, invite_config=invite_config,
@@ -94,8 +102,13 @@ class Patchioner(nn.Module):
         for k in _OUT_OF_SCOPE:
             if given[k] is not None:
                 raise NotImplementedError("%s: backbone/head outside the MI355X hot-path scope (DINOv2 + DeCap/CapDec)" % k)
-        if use_open_clip or online_texts is not None:
-            raise NotImplementedError("use_open_clip / online_texts need the CLIP text tower: outside the hot-path scope")
+        if use_open_clip:
+            raise NotImplementedError("use_open_clip: OpenCLIP text-tower weights are not supported (the OpenAI CLIP text tower "
+                                      "is: online_texts, bank.build_memory_bank)")
+        if online_texts is not None and (isinstance(online_texts, (str, bytes)) or not all(isinstance(t, str) for t in online_texts)):
+            raise TypeError("online_texts must be a list of str")
+        if online_texts is not None and support_memory_size > 0 and len(online_texts) == 0:
+            raise ValueError("online_texts is empty")
         # P/src/model.py:339-392: 'dinov2' names load from torch.hub, 'openai' names are the timm OpenAI-CLIP towers of the
         # "DeCap original" configurations (configs/decap_B16*.k.yaml, decap_B32.k.yaml)
         is_clip = dino_model is not None and 'openai' in dino_model and 'dinov2' not in dino_model
@@ -117,7 +130,7 @@ class Patchioner(nn.Module):
         self.text_dataset = memory_bank_texts
 
         # same validation order as the reference (P/src/model.py:144-162)
-        if projection_type in ('coco', 'msmarco', 'blip', 'vg', 'vg-test') or support_memory_size == 0:
+        if online_texts is not None or projection_type in ('coco', 'msmarco', 'blip', 'vg', 'vg-test') or support_memory_size == 0:
             pass
         elif projection_type is not None and os.path.exists(projection_type):
             pass
@@ -224,7 +237,16 @@ class Patchioner(nn.Module):
             self.viecap = VieCapHead(viecap_config, self.engine, clip_model_name)
 
         if support_memory_size > 0:
-            if memory_bank is not None:
+            if online_texts is not None:
+                # the reference's ONLINE_TEXTS bank (im2txtprojection.py:491-493, 551-553): the texts' features in order, no
+                # padding to support_memory_size; zero-norm rows are dropped below (engine.set_memory_bank)
+                texts = list(online_texts)
+                bank = self._online_bank(texts, dino_model, clip_model_name, use_talk2dino_project, linear_talk2dino,
+                                         clip_text_weights, clip_text_dtype, talk2dino_projection_weights, talk2dino_weights,
+                                         synthetic_seed)
+                bank = bank[bank.norm(dim=-1) != 0]
+                self.text_dataset = [t.encode() for t in texts]
+            elif memory_bank is not None:
                 bank, texts = load_memory_bank(memory_bank, want_texts=True)
                 if self.text_dataset is None:
                     self.text_dataset = texts
@@ -253,6 +275,32 @@ class Patchioner(nn.Module):
         self.dino = self.engine     # callers test `model.dino is not None`
         # one zero-size parameter so `next(model.parameters()).device` works as in the reference
         self._anchor = nn.Parameter(torch.zeros(0, device=self._device), requires_grad=False)
+
+    def _online_bank(self, texts, dino_model, clip_model_name, use_talk2dino, linear_talk2dino, clip_text_weights, clip_text_dtype,
+                     talk2dino_projection_weights, talk2dino_weights, synthetic_seed) -> torch.Tensor:
+        """CLIP text features of ``texts`` on the device (clip_text.ClipTextEncoder), through Talk2DINO's text projection
+        with ``use_talk2dino`` (bank.py: the same step as a bank build).  The text tower's device memory is freed here."""
+        from .bank import default_clip_model, talk2dino_text_weights
+        from .clip_text import ClipTextEncoder
+        name = clip_model_name or default_clip_model(use_talk2dino)
+        enc = ClipTextEncoder(name, weights=clip_text_weights, synthetic_seed=None if synthetic_seed is None else synthetic_seed + 5,
+                              operand_type=clip_text_dtype, device=self._device)
+        try:
+            feats = enc.encode_text(texts)
+        finally:
+            enc.close()
+        if not use_talk2dino:
+            return feats
+        t2d = _load_state_dict(talk2dino_projection_weights if talk2dino_projection_weights is not None else talk2dino_weights)
+        if t2d is None:
+            if synthetic_seed is None:
+                raise FileNotFoundError("online_texts with use_talk2dino_project needs the Talk2DINO projection: set "
+                                        "talk2dino_projection_weights or talk2dino_weights (or synthetic_seed)")
+            t2d = W.synth_talk2dino(synthetic_seed + 6, feats.shape[1], self.token_dim, hidden=not linear_talk2dino)
+        w = talk2dino_text_weights(t2d)
+        if linear_talk2dino:
+            w["w2"] = w["b2"] = None
+        return self.engine.text_project(feats, w["w1"], w["b1"], w["w2"], w["b2"], act="tanh")
 
     # ------------------------------------------------------------------------------------------
     @classmethod
@@ -299,6 +347,9 @@ class Patchioner(nn.Module):
             max_batch=config.get('max_batch', 16),
             max_prefixes=config.get('max_prefixes', 128),       # what ONE greedy decode serves (the engine's limit)
             vit_dtype=config.get('vit_dtype', 'fp16'),
+            clip_text_weights=config.get('clip_text_weights', None),
+            clip_text_dtype=config.get('clip_text_dtype', 'fp16'),
+            talk2dino_projection_weights=config.get('talk2dino_projection_weights', None),
         )
         model.to(device)
         return model

@@ -142,6 +142,64 @@ def add_outlier_channels(w: Dict[str, torch.Tensor], channels=(7, 300, 611), blo
     return w
 
 
+CLIP_TEXT_ARCHS = {
+    # clip.load name -> (width, layers, heads, embed_dim); context 77 and vocabulary 49 408 for all (clip/model.py build_model)
+    "ViT-B/16": (512, 12, 8, 512),
+    "ViT-B/32": (512, 12, 8, 512),
+    "ViT-L/14": (768, 12, 12, 768),
+    "ViT-L/14@336px": (768, 12, 12, 768),
+}
+
+
+def clip_text_arch(name: str):
+    if name not in CLIP_TEXT_ARCHS:
+        raise ValueError("unsupported CLIP model name %r (known: %s)" % (name, ", ".join(CLIP_TEXT_ARCHS)))
+    return CLIP_TEXT_ARCHS[name]
+
+
+def synth_clip_text(seed: int, name: str = "ViT-B/16", layers: int | None = None, context_length: int = 77,
+                    vocab_size: int = 49408) -> Dict[str, torch.Tensor]:
+    """State dict shaped like the text half of ``clip.load(name)[0].state_dict()``: token / positional embeddings,
+    ``transformer.resblocks.{i}`` (pre-LN, packed ``attn.in_proj_weight``, ``mlp.c_fc`` / ``mlp.c_proj``), ``ln_final`` and
+    ``text_projection`` [width, embed_dim]."""
+    W, full_layers, _, E = clip_text_arch(name)
+    layers = layers or full_layers
+    g = torch.Generator().manual_seed(seed)
+    w: Dict[str, torch.Tensor] = {}
+    w["token_embedding.weight"] = _tn(g, (vocab_size, W), 0.02)
+    w["positional_embedding"] = _tn(g, (context_length, W), 0.01)
+    for i in range(layers):
+        q = "transformer.resblocks.%d." % i
+        for ln in ("ln_1", "ln_2"):
+            w[q + ln + ".weight"] = 0.5 + torch.rand(W, generator=g)
+            w[q + ln + ".bias"] = _tn(g, (W,), 0.02)
+        qkv = _tn(g, (3 * W, W), 0.02)
+        qkv[: 2 * W] *= 2.5
+        w[q + "attn.in_proj_weight"] = qkv
+        w[q + "attn.in_proj_bias"] = _tn(g, (3 * W,), 0.02)
+        w[q + "attn.out_proj.weight"] = _tn(g, (W, W), 0.02) * 0.3
+        w[q + "attn.out_proj.bias"] = _tn(g, (W,), 0.02)
+        w[q + "mlp.c_fc.weight"] = _tn(g, (4 * W, W), 0.02)
+        w[q + "mlp.c_fc.bias"] = _tn(g, (4 * W,), 0.02)
+        w[q + "mlp.c_proj.weight"] = _tn(g, (W, 4 * W), 0.02) * 0.3
+        w[q + "mlp.c_proj.bias"] = _tn(g, (W,), 0.02)
+    w["ln_final.weight"] = 0.5 + torch.rand(W, generator=g)
+    w["ln_final.bias"] = _tn(g, (W,), 0.02)
+    w["text_projection"] = _tn(g, (W, E), W ** -0.5)
+    return w
+
+
+def synth_talk2dino(seed: int, clip_dim: int = 512, dino_dim: int = 768, hidden: bool = True) -> Dict[str, torch.Tensor]:
+    """A Talk2DINO ``ProjectionLayer`` state dict (P/src/talk2dino/talk2dino.py:73-90): ``linear_layer`` [dino_dim, clip_dim] and,
+    unless ``hidden`` is False (linear_talk2dino), ``hidden_layers.0`` [dino_dim, dino_dim]."""
+    g = torch.Generator().manual_seed(seed)
+    w = {"linear_layer.weight": _tn(g, (dino_dim, clip_dim), clip_dim ** -0.5), "linear_layer.bias": _tn(g, (dino_dim,), 0.02)}
+    if hidden:
+        w["hidden_layers.0.weight"] = _tn(g, (dino_dim, dino_dim), dino_dim ** -0.5)
+        w["hidden_layers.0.bias"] = _tn(g, (dino_dim,), 0.02)
+    return w
+
+
 def synth_decap(seed: int, prefix_size: int = 768, n_layer: int = 4, n_embd: int = 768,
                 vocab: int = 50257, n_positions: int = 1024, tok_vocab: int = 49408,
                 std: float = 0.02) -> Dict[str, torch.Tensor]:
