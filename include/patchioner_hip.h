@@ -235,6 +235,23 @@ int pio_lm_score(pio_handle h, const int32_t* tokens, const int32_t* lens, int32
 int pio_viecap_decode(pio_handle h, const float* cont, const int32_t* tokens, int32_t N, int32_t Lt, int32_t soft_first,
                       int32_t steps, int32_t* ids, pio_stream stream);
 
+/* The hard prompt on the device (the pipelined head): top_entities + compose_discrete_prompts + tokenisation + pad_sequence.
+ * probs [N, K] = pio_viecap_entity_logits' output.  Entities are taken in torch.topk order (descending probability, equal values by the
+ * lower index, NaN first) up to top_k (1..8), cut at the first probability < threshold.  The token row is the concatenation of fragments
+ * of frag_ids: [head_off, +head_len) then, per chosen entity e, its middle fragment (frag_off / frag_len [2e]) or, for the last one, its
+ * last fragment ([2e + 1]); no entity: [empty_off, +empty_len).  seg [N]: caption call of each row (NULL: one call); rows are padded with
+ * pad_id to Lmax and lens[n] = the longest row of row n's call (what pad_sequence makes the reference feed the language model).
+ * tokens [N, Lmax] int32, lens [N] int32, scratch [N] int32; all device memory, nothing waits for the device. */
+int pio_viecap_compose_prompts(pio_handle h, const float* probs, int32_t N, int32_t K, const int32_t* frag_ids, const int32_t* frag_off,
+                               const int32_t* frag_len, int32_t head_off, int32_t head_len, int32_t empty_off, int32_t empty_len,
+                               int32_t top_k, float threshold, int32_t pad_id, const int32_t* seg, int32_t Lmax, int32_t* tokens,
+                               int32_t* lens, int32_t* scratch, pio_stream stream);
+/* pio_viecap_decode with a hard-prompt length per row: row n's prompt is cont[n] and tokens[n, :lens[n]] (lens on the device,
+ * 0 <= lens[n] <= Ltmax), i.e. P_n = Lc + lens[n] positions; its ids equal those of pio_viecap_decode on that row alone with
+ * Lt = lens[n].  The graph depends on (N, Lc + Ltmax, steps) only.  Works on decoder clones (pio_clone_decoder). */
+int pio_viecap_decode_ragged(pio_handle h, const float* cont, const int32_t* tokens, const int32_t* lens, int32_t N, int32_t Ltmax,
+                             int32_t soft_first, int32_t steps, int32_t* ids, pio_stream stream);
+
 /* beam_search (P/src/viecap/search.py:193-285; VieCap.forward calls it per image when using_greedy_search is false,
  * entrypoint.py:143-148) as three device steps; the bookkeeping between them (token lists, lengths, stop flags) is the caller's.
  * The W beams of an image are the N rows of these calls and keep KV caches on the handle (the reference re-runs every beam's whole

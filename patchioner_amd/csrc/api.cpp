@@ -143,7 +143,14 @@ struct pio_context {
   float *pre_x = nullptr, *pre_qkv = nullptr, *pre_att = nullptr, *pre_hid = nullptr;   // batched prompt prefill (decoder.hip), kPrefillRows rows
   static constexpr int kPrefillRows = 2048;
   int32_t* tok_buf = nullptr;                     // [max_prefixes][max_steps]
-  struct PKey { int N, P, steps; bool operator<(const PKey& o) const { return N != o.N ? N < o.N : (P != o.P ? P < o.P : steps < o.steps); } };
+  int32_t* plen_buf = nullptr;                    // [max_prefixes] prompt length per row of a ragged decode (pio_viecap_decode_ragged)
+  // ragged: a pio_viecap_decode_ragged graph (P = the upper bound Pmax; the lengths are read from plen_buf)
+  struct PKey {
+    int N, P, steps, ragged;
+    bool operator<(const PKey& o) const {
+      return N != o.N ? N < o.N : (P != o.P ? P < o.P : (steps != o.steps ? steps < o.steps : ragged < o.ragged));
+    }
+  };
   // prompted-decode graphs, keyed by (rows, prompt positions, steps).  The prompt length follows the hard prompt of every batch,
   // so a long run meets many keys: the cache is a small LRU (a graph is ~ (P + steps) x 60 kernel nodes) and evicted execs are destroyed.
   struct PGraph { hipGraphExec_t exec; uint64_t last_use; hipEvent_t done; };     // done: recorded behind the graph's last launch (valid after the caller's stream has gone)
@@ -1417,6 +1424,79 @@ int pio_beam_select(pio_handle c, const float* logp, const float* scores, const 
   return PIO_OK;
 }
 
+// The device hard prompt and the ragged decode are referenced weakly: the host-only AddressSanitizer build of this file
+// (tests/hipstub) links it against stubs of the launchers it has always had, without the kernels; there these entry points report
+// PIO_ERR_NOT_READY.  The library itself always defines them (viecap.hip, decoder.hip).
+extern "C++" {
+namespace pio {
+hipError_t launch_compose_prompts(const ComposeArgs& a, hipStream_t s) __attribute__((weak));
+hipError_t launch_build_prompt_ragged(const float* cont, const int32_t* tokens, const int32_t* lt, const float* wte, int N, int Lc, int Ltmax,
+                                      int E, int V, int soft_first, float* prompt, int32_t* plen, hipStream_t s) __attribute__((weak));
+hipError_t launch_decode_prompted_ragged(const DecoderArgs& a, const float* prompt, int Pmax, const int32_t* plen, int split, hipStream_t s)
+    __attribute__((weak));
+}  // namespace pio
+}  // extern "C++"
+
+// Launch a prompted decode through the handle's graph cache: captured on first use of `key`, a small LRU (see pgraphs).
+extern "C++" {
+template <class F>
+static int launch_prompted_graph(pio_context* c, const pio_context::PKey& key, F launch, hipStream_t s) {
+  auto it = c->pgraphs.find(key);
+  if (it == c->pgraphs.end()) {
+    hipGraph_t graph = nullptr;
+    HIP_OK(hipStreamBeginCapture(c->capture_stream, hipStreamCaptureModeThreadLocal));
+    hipError_t le = launch(c->capture_stream);
+    hipError_t ce = hipStreamEndCapture(c->capture_stream, &graph);
+    if (le != hipSuccess) {
+      if (graph) (void)hipGraphDestroy(graph);
+      return fail(PIO_ERR_HIP, std::string("prompted decode capture: ") + hipGetErrorString(le));
+    }
+    HIP_OK(ce);
+    hipGraphExec_t exec = nullptr;
+    hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    HIP_OK(ie);
+    if (c->pgraphs.size() >= pio_context::kMaxPGraphs) {       // evict the least recently used graph
+      auto old = c->pgraphs.begin();
+      for (auto jt = c->pgraphs.begin(); jt != c->pgraphs.end(); ++jt)
+        if (jt->second.last_use < old->second.last_use) old = jt;
+      // it may still be running where it was last launched: wait for the event recorded behind that launch (an event outlives the
+      // caller's stream; round 4 synchronised the stored stream handle, which a caller may have destroyed since -- the error then
+      // left the new exec leaked and the dead entry in place for every later decode).  Whatever the wait says, the entry goes.
+      if (old->second.done) { (void)hipEventSynchronize(old->second.done); (void)hipEventDestroy(old->second.done); }
+      (void)hipGraphExecDestroy(old->second.exec);
+      c->pgraphs.erase(old);
+    }
+    hipEvent_t done = nullptr;
+    const hipError_t ee = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+    if (ee != hipSuccess) { (void)hipGraphExecDestroy(exec); HIP_OK(ee); }
+    it = c->pgraphs.emplace(key, pio_context::PGraph{exec, 0, done}).first;
+  }
+  it->second.last_use = ++c->pgraph_clock;
+  HIP_OK(hipGraphLaunch(it->second.exec, s));
+  HIP_OK(hipEventRecord(it->second.done, s));
+  return PIO_OK;
+}
+}  // extern "C++"
+
+// prompt buffer and batched-prefill workspace of the prompted decodes, allocated on first use
+static int prompted_workspaces(pio_context* c, bool prefill) {
+  const int E = c->cfg.dec_embd;
+  int rc;
+  if (!c->prompt_buf) {
+    if ((rc = c->dmalloc(&c->prompt_buf, (size_t)c->cfg.max_prefixes * c->cfg.max_steps * E))) return rc;
+    if ((rc = c->dmalloc(&c->tok_buf, (size_t)c->cfg.max_prefixes * c->cfg.max_steps))) return rc;
+  }
+  if (prefill && !c->pre_x) {                         // workspace of the batched prompt prefill: 2 048 rows (56 MB)
+    const size_t R = pio_context::kPrefillRows;
+    if ((rc = c->dmalloc(&c->pre_x, R * E))) return rc;
+    if ((rc = c->dmalloc(&c->pre_qkv, R * 3 * E))) return rc;
+    if ((rc = c->dmalloc(&c->pre_att, R * E))) return rc;
+    if ((rc = c->dmalloc(&c->pre_hid, R * 4 * E))) return rc;
+  }
+  return PIO_OK;
+}
+
 int pio_viecap_decode(pio_handle c, const float* cont, const int32_t* tokens, int32_t N, int32_t Lt, int32_t soft_first,
                       int32_t steps, int32_t* ids, pio_stream stream) {
   if (!c || !ids || (Lt > 0 && !tokens)) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode: null argument");
@@ -1431,18 +1511,8 @@ int pio_viecap_decode(pio_handle c, const float* cont, const int32_t* tokens, in
   hipStream_t s = (hipStream_t)stream;
   const int E = c->cfg.dec_embd;
   int rc;
-  if (!c->prompt_buf) {
-    if ((rc = c->dmalloc(&c->prompt_buf, (size_t)c->cfg.max_prefixes * c->cfg.max_steps * E))) return rc;
-    if ((rc = c->dmalloc(&c->tok_buf, (size_t)c->cfg.max_prefixes * c->cfg.max_steps))) return rc;
-  }
   const bool batched_prefill = c->batched_prefill;
-  if (batched_prefill && !c->pre_x) {                 // workspace of the batched prompt prefill: 2 048 rows (56 MB)
-    const size_t R = pio_context::kPrefillRows;
-    if ((rc = c->dmalloc(&c->pre_x, R * E))) return rc;
-    if ((rc = c->dmalloc(&c->pre_qkv, R * 3 * E))) return rc;
-    if ((rc = c->dmalloc(&c->pre_att, R * E))) return rc;
-    if ((rc = c->dmalloc(&c->pre_hid, R * 4 * E))) return rc;
-  }
+  if ((rc = prompted_workspaces(c, batched_prefill))) return rc;
   if (Lt > 0) HIP_OK(hipMemcpyAsync(c->tok_buf, tokens, (size_t)N * Lt * 4, hipMemcpyDeviceToDevice, s));
   HIP_OK(launch_build_prompt(cont, c->tok_buf, c->wte, N, Lc, Lt, E, c->cfg.dec_vocab, soft_first, c->prompt_buf, s));
   DecoderArgs a;
@@ -1456,43 +1526,76 @@ int pio_viecap_decode(pio_handle c, const float* cont, const int32_t* tokens, in
   if (batched_prefill) { a.pre_x = c->pre_x; a.pre_qkv = c->pre_qkv; a.pre_att = c->pre_att; a.pre_hid = c->pre_hid; a.pre_rows = pio_context::kPrefillRows; }
   HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
   if (c->use_graph) {
-    const pio_context::PKey key{N, P, steps};
-    auto it = c->pgraphs.find(key);
-    if (it == c->pgraphs.end()) {
-      hipGraph_t graph = nullptr;
-      HIP_OK(hipStreamBeginCapture(c->capture_stream, hipStreamCaptureModeThreadLocal));
-      hipError_t le = launch_decode_prompted(a, c->prompt_buf, P, c->capture_stream);
-      hipError_t ce = hipStreamEndCapture(c->capture_stream, &graph);
-      if (le != hipSuccess) {
-        if (graph) (void)hipGraphDestroy(graph);
-        return fail(PIO_ERR_HIP, std::string("prompted decode capture: ") + hipGetErrorString(le));
-      }
-      HIP_OK(ce);
-      hipGraphExec_t exec = nullptr;
-      hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      HIP_OK(ie);
-      if (c->pgraphs.size() >= pio_context::kMaxPGraphs) {       // evict the least recently used graph
-        auto old = c->pgraphs.begin();
-        for (auto jt = c->pgraphs.begin(); jt != c->pgraphs.end(); ++jt)
-          if (jt->second.last_use < old->second.last_use) old = jt;
-        // it may still be running where it was last launched: wait for the event recorded behind that launch (an event outlives the
-        // caller's stream; round 4 synchronised the stored stream handle, which a caller may have destroyed since -- the error then
-        // left the new exec leaked and the dead entry in place for every later decode).  Whatever the wait says, the entry goes.
-        if (old->second.done) { (void)hipEventSynchronize(old->second.done); (void)hipEventDestroy(old->second.done); }
-        (void)hipGraphExecDestroy(old->second.exec);
-        c->pgraphs.erase(old);
-      }
-      hipEvent_t done = nullptr;
-      const hipError_t ee = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-      if (ee != hipSuccess) { (void)hipGraphExecDestroy(exec); HIP_OK(ee); }
-      it = c->pgraphs.emplace(key, pio_context::PGraph{exec, 0, done}).first;
-    }
-    it->second.last_use = ++c->pgraph_clock;
-    HIP_OK(hipGraphLaunch(it->second.exec, s));
-    HIP_OK(hipEventRecord(it->second.done, s));
+    int rc2 = launch_prompted_graph(c, pio_context::PKey{N, P, steps, 0},
+                                    [&](hipStream_t cs) { return launch_decode_prompted(a, c->prompt_buf, P, cs); }, s);
+    if (rc2) return rc2;
   } else {
     HIP_OK(launch_decode_prompted(a, c->prompt_buf, P, s));
+  }
+  HIP_OK(hipMemcpyAsync(ids, c->ids_buf, (size_t)N * steps * 4, hipMemcpyDeviceToDevice, s));
+  return PIO_OK;
+}
+
+int pio_viecap_compose_prompts(pio_handle c, const float* probs, int32_t N, int32_t K, const int32_t* frag_ids, const int32_t* frag_off,
+                               const int32_t* frag_len, int32_t head_off, int32_t head_len, int32_t empty_off, int32_t empty_len,
+                               int32_t top_k, float threshold, int32_t pad_id, const int32_t* seg, int32_t Lmax, int32_t* tokens,
+                               int32_t* lens, int32_t* scratch, pio_stream stream) {
+  if (!c || !probs || !frag_ids || !frag_off || !frag_len || !tokens || !lens || !scratch)
+    return fail(PIO_ERR_INVALID_ARG, "pio_viecap_compose_prompts: null argument");
+  if (N < 1 || K < 1 || Lmax < 1 || head_len < 0 || empty_len < 0 || head_off < 0 || empty_off < 0)
+    return fail(PIO_ERR_INVALID_ARG, "pio_viecap_compose_prompts: bad shape");
+  if (top_k < 1 || top_k > 8) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_compose_prompts: top_k must be 1..8");
+  if (!launch_compose_prompts) return fail(PIO_ERR_NOT_READY, "pio_viecap_compose_prompts: built without the kernels");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  ComposeArgs a;
+  a.probs = probs; a.N = N; a.K = K; a.frag_ids = frag_ids; a.frag_off = frag_off; a.frag_len = frag_len;
+  a.head_off = head_off; a.head_len = head_len; a.empty_off = empty_off; a.empty_len = empty_len;
+  a.top_k = top_k; a.threshold = threshold; a.pad_id = pad_id; a.seg = seg; a.Lmax = Lmax;
+  a.tokens = tokens; a.lens = lens; a.rawlen = scratch;
+  HIP_OK(launch_compose_prompts(a, (hipStream_t)stream));
+  return PIO_OK;
+}
+
+int pio_viecap_decode_ragged(pio_handle c, const float* cont, const int32_t* tokens, const int32_t* lens, int32_t N, int32_t Ltmax,
+                             int32_t soft_first, int32_t steps, int32_t* ids, pio_stream stream) {
+  if (!c || !ids || (Ltmax > 0 && (!tokens || !lens))) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode_ragged: null argument");
+  if (!cont && Ltmax < 1) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode_ragged: neither a soft prompt nor prompt tokens");
+  const pio_context* owner = c->parent ? c->parent : c;      // a decoder clone reads the mapping network's prompt length from its owner
+  if (!c->has_dec || (cont && !owner->has_map)) return fail(PIO_ERR_NOT_READY, "pio_viecap_decode_ragged: language model / mapping network not loaded");
+  if (N < 1 || N > c->cfg.max_prefixes || N > 128) return fail(PIO_ERR_CAPACITY, "pio_viecap_decode_ragged: N above min(max_prefixes, 128)");
+  if (c->lm_tail) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode_ragged: the ticketed LM-head tail (PIO_LM_TAIL=1) has no ragged form");
+  if (!launch_build_prompt_ragged || !launch_decode_prompted_ragged) return fail(PIO_ERR_NOT_READY, "pio_viecap_decode_ragged: built without the kernels");
+  const int Lc = cont ? owner->map_Lc : 0;
+  const int Pmax = Lc + Ltmax;
+  if (Ltmax < 0 || steps < 1 || steps > 64 || Pmax + steps - 1 > c->cfg.max_steps)
+    return fail(PIO_ERR_CAPACITY, "pio_viecap_decode_ragged: prompt + generated positions above max_steps");
+  if (Pmax > 128) return fail(PIO_ERR_CAPACITY, "pio_viecap_decode_ragged: soft prompt + longest hard prompt above 128 positions");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  const int E = c->cfg.dec_embd;
+  int rc;
+  if ((rc = prompted_workspaces(c, true))) return rc;          // the ragged decode always takes its prompt through the batched prefill
+  if (!c->plen_buf && (rc = c->dmalloc(&c->plen_buf, (size_t)c->cfg.max_prefixes))) return rc;
+  HIP_OK(launch_build_prompt_ragged(cont, tokens, Ltmax > 0 ? lens : nullptr, c->wte, N, Lc, Ltmax, E, c->cfg.dec_vocab, soft_first,
+                                    c->prompt_buf, c->plen_buf, s));
+  DecoderArgs a;
+  a.N = N; a.steps = steps; a.E = E; a.heads = c->cfg.dec_heads; a.layers = c->cfg.dec_layers; a.vocab = c->cfg.dec_vocab;
+  a.prefix_size = c->cfg.prefix_size; a.eps = c->cfg.dec_ln_eps; a.prefix = nullptr; a.clip_w = nullptr; a.clip_b = nullptr;
+  a.wte = c->wte; a.wpe = c->wpe; a.head_w = c->head_w; a.head_c = c->head_c; a.head_d = c->head_d; a.layer = c->dl.data();
+  a.x = c->dx; a.qkv = c->dqkv; a.att = c->datt; a.hid = c->dhid; a.splitk_ws = c->splitk_ws; a.splitk_cnt = c->splitk_cnt; a.lm_tail = 0;
+  a.kcache = c->kcache; a.vcache = c->vcache; a.max_steps = c->cfg.max_steps; a.logits = c->logits; a.ids = c->ids_buf; a.logprob = nullptr;
+  a.head_w16 = c->head_w16; a.head_w16_unscale = c->head_w16_unscale; a.head_bound_coef = c->head_bound_coef;
+  a.xh = c->dec_xh; a.lm_stats = c->lm_stats; a.lm_gmax = c->lm_gmax; a.pos_base = 0;
+  a.pre_x = c->pre_x; a.pre_qkv = c->pre_qkv; a.pre_att = c->pre_att; a.pre_hid = c->pre_hid; a.pre_rows = pio_context::kPrefillRows;
+  HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
+  const int32_t* plen = c->plen_buf;
+  const int split = c->batched_prefill ? 16 : 256;      // the prompt lengths pio_viecap_decode prefills on one row group (decoder.hip)
+  if (c->use_graph) {
+    if ((rc = launch_prompted_graph(c, pio_context::PKey{N, Pmax, steps, 1},
+                                    [&](hipStream_t cs) { return launch_decode_prompted_ragged(a, c->prompt_buf, Pmax, plen, split, cs); }, s)))
+      return rc;
+  } else {
+    HIP_OK(launch_decode_prompted_ragged(a, c->prompt_buf, Pmax, plen, split, s));
   }
   HIP_OK(hipMemcpyAsync(ids, c->ids_buf, (size_t)N * steps * 4, hipMemcpyDeviceToDevice, s));
   return PIO_OK;

@@ -416,12 +416,20 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? PIO_DEC_GEMM_WAVES : 1) void k
 // grid.y > 1 (batched prompt prefill, dec_prefill_layers): workgroup (x, y) handles position pos0 + y of prefix n, whose activations are
 // row n * rows_per_n + y of qkv / att; the keys and values of ALL those positions have been appended by k_kv_append before the launch
 // (the workgroup's own append below then rewrites the values that are there).  Same loads, same order per (prefix, head, position).
+// RAG (ragged prompted decode, grid.y == 1): prefix n's new position is plen[n] + pos0 (its own prompt length plus the step), read from
+// device memory; the loop bodies are the uniform kernel's, so a row attends over its keys exactly as the uniform kernel does for that count.
+// MASK (ragged prefill, decoder.hip: launch_decode_prompted_ragged): 1 = append keys / values only for prefixes with plen[n] <= split,
+// 2 = only for plen[n] > split; the others keep what the other prefill pass wrote.  Everything else is the uniform kernel.
+template <bool RAG = false, int MASK = 0>
 __global__ __launch_bounds__(256) void k_dec_attention(const float* __restrict__ qkv, float* kcache, float* vcache,
-                                                       int E, int heads, int pos0, int max_steps, float* att, int rows_per_n) {
+                                                       int E, int heads, int pos0, int max_steps, float* att, int rows_per_n,
+                                                       const int32_t* __restrict__ plen = nullptr, int split = 0) {
   __shared__ float s_sc[256];
   __shared__ __attribute__((aligned(16))) float s_o[5][256];
   const int n = blockIdx.x / heads, h = blockIdx.x - n * heads;
-  const int pos = pos0 + (int)blockIdx.y;
+  int pos;
+  if constexpr (RAG) pos = plen[n] + pos0;
+  else pos = pos0 + (int)blockIdx.y;
   const size_t row = (size_t)n * rows_per_n + blockIdx.y;
   const int tid = threadIdx.x;
   const int hd = E / heads;                      // 192; multiple of 32
@@ -461,7 +469,9 @@ __global__ __launch_bounds__(256) void k_dec_attention(const float* __restrict__
       if (seg == 0 && j <= pos) s_sc[j] = s * scale;
     }
   }
-  if (tid < hd) {                                  // append the new key / value
+  bool append = true;
+  if constexpr (MASK != 0) append = (plen[n] <= split) == (MASK == 1);
+  if (tid < hd && append) {                        // append the new key / value
     kc[(size_t)pos * E + tid] = kn[tid];
     vc[(size_t)pos * E + tid] = vn[tid];
   }
@@ -511,14 +521,17 @@ __global__ __launch_bounds__(256) void k_dec_attention(const float* __restrict__
 // Merge the LM head's per-workgroup (max, arg-max, sum-exp) partials: greedy id (first index on ties, like
 // torch.argmax), log-softmax of the chosen logit; then the next step's input x = wte[id] + wpe[step+1].
 // One workgroup per prefix.
+// RAG: the row's pos_base is plen[n] - 1 (ragged prompted decode) instead of the argument.
+template <bool RAG = false>
 __global__ __launch_bounds__(256) void k_dec_select(const float* __restrict__ part, int nblk, int N, int E, int step,
                                                     int steps, const float* __restrict__ wte,
                                                     const float* __restrict__ wpe, int32_t* ids, float* logprob,
-                                                    float* x, int pos_base) {
+                                                    float* x, int pos_base, const int32_t* __restrict__ plen = nullptr) {
   __shared__ float s_v[4];
   __shared__ int s_i[4];
   __shared__ float s_s[4];
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if constexpr (RAG) pos_base = plen[n] - 1;
   // each thread keeps its <= 16 partials (nblk <= 4096) in registers: one 16-B load each, all in flight
   float4 pr[16];
 #pragma unroll
@@ -1253,6 +1266,52 @@ static hipError_t dec_gemm(const float* W, const float* X, int N, int Nout, int 
   return hipErrorInvalidValue;
 }
 
+// ---- GEMMs of the ragged prompted decode: one kernel family whatever the row count --------------------------------------------
+// dec_gemm picks its kernel by the rows of a launch, and the kernels sum a row in different orders (k_dec_gemm: wave w owns k in
+// [192 w, 192 w + 192), k_dec_gemm_b: wave kw owns the kw-th 16 k of every 64-k chunk; k_dec_gemm_s: split-fp16 operands).  Inside one
+// family a row's sums do not depend on the other rows: k_dec_gemm<RG, 12, KS, ., ., 4> runs the same MFMA chain per row for any RG
+// (RG only repeats it over row groups; the X-through-LDS form at RG = 1 has the same values and order), k_dec_gemm_b the same for any
+// tile (RGB, NCG); split-K slabs are added in slice order in both.  So the ragged decode names the family:
+//   DEC_CLS_A = k_dec_gemm with 4 waves x 12 chunks -- what a decode of <= 16 rows and a prefill of <= 16 prompt rows run;
+//   DEC_CLS_B = k_dec_gemm_b                         -- what the batched prefill of 17 .. 128 prompt rows runs.
+enum DecCls { DEC_CLS_A = 0, DEC_CLS_B = 1 };
+template <int EPI, int LN>
+static hipError_t dec_gemm_cls(int cls, const float* W, const float* X, int N, int Nout, int K, const float* bias, float* out,
+                               const float* cvec, float eps, float* ws, unsigned* cnt, hipStream_t s) {
+  if (N < 1 || N > 128) return hipErrorInvalidValue;
+  const int rg = ceil_div(N, 16);
+  if (cls == DEC_CLS_B) {
+    if (K == 768 && Nout % 48 == 0) {
+      const bool wide = Nout >= 2304;
+      if (rg > 4) return wide ? dec_gemm_b_launch<2, 3, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s)
+                              : dec_gemm_b_launch<2, 1, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
+      if (rg > 2) return wide ? dec_gemm_b_launch<2, 2, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s)
+                              : dec_gemm_b_launch<1, 1, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
+      return wide ? dec_gemm_b_launch<1, 2, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s)
+                  : dec_gemm_b_launch<1, 1, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
+    }
+    if constexpr (EPI == DE_RESID && !LN) {
+      if (K == 3072 && Nout % 32 == 0 && Nout <= 1024 && ws != nullptr && cnt != nullptr) {
+        if (rg > 4) return dec_gemm_b_launch<4, 2, 4, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
+        if (rg > 2) return dec_gemm_b_launch<2, 2, 4, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
+        return dec_gemm_b_launch<1, 2, 4, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
+      }
+    }
+    return hipErrorInvalidValue;
+  }
+  const int KS = K == 768 ? 1 : (K == 3072 ? 4 : 0);
+  if (KS == 0 || (KS == 4 && (EPI != DE_RESID || LN || ws == nullptr || cnt == nullptr || Nout > 1024))) return hipErrorInvalidValue;
+  const dim3 grid(ceil_div(Nout, 16), KS);
+#define PIO_DGA(R, KSV) hipLaunchKernelGGL((k_dec_gemm<R, 12, KSV, EPI, LN, 4>), grid, dim3(256), 0, s, W, X, N, Nout, K, bias, out, nullptr, cvec, eps, ws, cnt)
+  if (KS == 1) {
+    if (rg <= 1) PIO_DGA(1, 1); else if (rg <= 2) PIO_DGA(2, 1); else if (rg <= 4) PIO_DGA(4, 1); else PIO_DGA(8, 1);
+  } else if constexpr (EPI == DE_RESID && !LN) {
+    if (rg <= 1) PIO_DGA(1, 4); else if (rg <= 2) PIO_DGA(2, 4); else if (rg <= 4) PIO_DGA(4, 4); else PIO_DGA(8, 4);
+  }
+#undef PIO_DGA
+  return hipGetLastError();
+}
+
 hipError_t decoder_init() { return hipSuccess; }   // no function attributes needed any more
 
 #define PIO_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
@@ -1716,13 +1775,15 @@ __device__ __forceinline__ void dec_select_row(const int n, const float4 st, con
   if (tid == 0) ids[(size_t)n * steps + step] = best_i;
 }
 
+template <bool RAG = false>
 __global__ __launch_bounds__(256) void k_dec_select_filter(const float* __restrict__ approx, const float* __restrict__ gmax, int V, int Vp,
                                                            int NG, int NGp, const float* __restrict__ stats,
                                                            const float* xrow, const float* __restrict__ W /*[V][E] LN-folded*/,
                                                            const float* __restrict__ dvec, const float* __restrict__ cvec, int E, int step,
                                                            int steps, const float* __restrict__ wte, const float* __restrict__ wpe,
-                                                           int32_t* ids, float* x, int pos_base) {
+                                                           int32_t* ids, float* x, int pos_base, const int32_t* __restrict__ plen = nullptr) {
   const int n = blockIdx.x;
+  if constexpr (RAG) pos_base = plen[n] - 1;
   dec_select_row<false>(n, *(const float4*)(stats + 4 * n), approx, gmax, V, Vp, NG, NGp, xrow, W, dvec, cvec, E, step, steps, wte, wpe, ids, x, pos_base);
 }
 
@@ -1894,7 +1955,8 @@ static hipError_t launch_lmhead_f16(const DecoderArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-static hipError_t launch_lmhead_filtered(const DecoderArgs& a, int step, hipStream_t s) {
+template <bool RAG = false>
+static hipError_t launch_lmhead_filtered(const DecoderArgs& a, int step, hipStream_t s, const int32_t* plen = nullptr) {
   const int Vp = round_up(a.vocab, 64);
   hipError_t e;
   const int rg = ceil_div(a.N, 16);
@@ -1905,7 +1967,7 @@ static hipError_t launch_lmhead_filtered(const DecoderArgs& a, int step, hipStre
     // Built for VERDICT r4 and MEASURED SLOWER, so it is off: decode(16) 4.285 against 4.15 ms, decode(1) 3.90 against 3.79 (two alternations on one
     // box, ids identical) -- the written-through stores, their drain in every workgroup, the ticket and the agent-scope re-reads cost
     // ~9 us per step where the separate launch costs ~5.8 + its gap.
-    if (a.lm_tail && a.splitk_cnt != nullptr && a.N <= nwg) {
+    if (!RAG && a.lm_tail && a.splitk_cnt != nullptr && a.N <= nwg) {   // (the ticketed tail has no ragged form)
       const LmTail tl{a.splitk_cnt + DEC_SPLITK_COUNTERS, a.head_w, a.E, step, a.steps, a.wte, a.wpe, a.ids, a.x, a.pos_base, NG1};
       hipLaunchKernelGGL(k_lmhead_f16_fused<true>, dim3(nwg), dim3(256), 0, s, a.head_w16, a.x, a.N, a.vocab, Vp, a.eps,
                          a.head_bound_coef, a.lm_stats, a.head_d, a.head_c, a.head_w16_unscale, a.logits, a.lm_gmax, NGp1, tl);
@@ -1926,8 +1988,8 @@ static hipError_t launch_lmhead_filtered(const DecoderArgs& a, int step, hipStre
   if (e != hipSuccess) return e;
   const int NG = ceil_div(a.vocab, 16), NGp = round_up(NG, 64);
   if (NG > 4096) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_dec_select_filter, dim3(a.N), dim3(256), 0, s, a.logits, a.lm_gmax, a.vocab, Vp, NG, NGp, a.lm_stats, a.x,
-                     a.head_w, a.head_d, a.head_c, a.E, step, a.steps, a.wte, a.wpe, a.ids, a.x, a.pos_base);
+  hipLaunchKernelGGL(k_dec_select_filter<RAG>, dim3(a.N), dim3(256), 0, s, a.logits, a.lm_gmax, a.vocab, Vp, NG, NGp, a.lm_stats, a.x,
+                     a.head_w, a.head_d, a.head_c, a.E, step, a.steps, a.wte, a.wpe, a.ids, a.x, a.pos_base, plen);
   return hipGetLastError();
 }
 
@@ -1948,14 +2010,24 @@ hipError_t launch_lmhead(const float* W, const float* X, int N, int V, int E, co
 }
 
 // One new position `pos` of every prefix through the transformer layers (x in place; keys / values appended at `pos`).
-static hipError_t dec_layers_step(const DecoderArgs& a, int pos, hipStream_t s) {
+// RAG: prefix n's position is plen[n] + pos.
+template <bool RAG = false>
+static hipError_t dec_layers_step(const DecoderArgs& a, int pos, hipStream_t s, const int32_t* plen = nullptr) {
   const int N = a.N, E = a.E;
   for (int l = 0; l < a.layers; ++l) {
     const DecLayerW& w = a.layer[l];
     float* kc = a.kcache + (size_t)l * N * a.max_steps * E;
     float* vc = a.vcache + (size_t)l * N * a.max_steps * E;
+    if constexpr (RAG) {             // every row on the kernels of a one-row decode, whatever the rows of the launch (dec_gemm_cls)
+      PIO_TRY((dec_gemm_cls<DE_STORE, 1>(DEC_CLS_A, w.attn_w, a.x, N, 3 * E, E, w.attn_d, a.qkv, w.attn_c, a.eps, nullptr, nullptr, s)));
+      hipLaunchKernelGGL(k_dec_attention<true>, dim3(N * a.heads), dim3(256), 0, s, a.qkv, kc, vc, E, a.heads, pos, a.max_steps, a.att, 1, plen, 0);
+      PIO_TRY((dec_gemm_cls<DE_RESID, 0>(DEC_CLS_A, w.proj_w, a.att, N, E, E, w.proj_b, a.x, nullptr, 0.f, nullptr, nullptr, s)));
+      PIO_TRY((dec_gemm_cls<DE_GELU, 1>(DEC_CLS_A, w.fc_w, a.x, N, 4 * E, E, w.fc_d, a.hid, w.fc_c, a.eps, nullptr, nullptr, s)));
+      PIO_TRY((dec_gemm_cls<DE_RESID, 0>(DEC_CLS_A, w.fc2_w, a.hid, N, E, 4 * E, w.fc2_b, a.x, nullptr, 0.f, a.splitk_ws, a.splitk_cnt, s)));
+      continue;
+    }
     PIO_TRY((dec_gemm<DE_STORE, 1>(w.attn_w, a.x, N, 3 * E, E, w.attn_d, a.qkv, nullptr, w.attn_c, a.eps, nullptr, nullptr, s, w.attn_ws, w.attn_un)));
-    hipLaunchKernelGGL(k_dec_attention, dim3(N * a.heads), dim3(256), 0, s, a.qkv, kc, vc, E, a.heads, pos, a.max_steps, a.att, 1);
+    hipLaunchKernelGGL(k_dec_attention<false>, dim3(N * a.heads), dim3(256), 0, s, a.qkv, kc, vc, E, a.heads, pos, a.max_steps, a.att, 1, nullptr, 0);
     PIO_TRY((dec_gemm<DE_RESID, 0>(w.proj_w, a.att, N, E, E, w.proj_b, a.x, nullptr, nullptr, 0.f, nullptr, nullptr, s)));
     PIO_TRY((dec_gemm<DE_GELU, 1>(w.fc_w, a.x, N, 4 * E, E, w.fc_d, a.hid, nullptr, w.fc_c, a.eps, nullptr, nullptr, s, w.fc_ws, w.fc_un)));
     PIO_TRY((dec_gemm<DE_RESID, 0>(w.fc2_w, a.hid, N, E, 4 * E, w.fc2_b, a.x, nullptr, nullptr, 0.f, a.splitk_ws, a.splitk_cnt, s, w.fc2_ws, w.fc2_un)));
@@ -1964,12 +2036,14 @@ static hipError_t dec_layers_step(const DecoderArgs& a, int pos, hipStream_t s) 
 }
 
 // LM head on x -> ids[.][step] (+ log-prob) and the next position's input x = wte[id] + wpe[pos_base + step + 1]
-static hipError_t dec_head_step(const DecoderArgs& a, int step, bool filtered, hipStream_t s) {
-  if (filtered) return launch_lmhead_filtered(a, step, s);
+// RAG: x = wte[id] + wpe[plen[n] + step] per row.
+template <bool RAG = false>
+static hipError_t dec_head_step(const DecoderArgs& a, int step, bool filtered, hipStream_t s, const int32_t* plen = nullptr) {
+  if (filtered) return launch_lmhead_filtered<RAG>(a, step, s, plen);
   int nblk = 0;
   PIO_TRY(launch_lmhead(a.head_w, a.x, a.N, a.vocab, a.E, a.head_d, a.head_c, a.eps, a.logits, &nblk, s));
-  hipLaunchKernelGGL(k_dec_select, dim3(a.N), dim3(256), 0, s, a.logits, nblk, a.N, a.E, step, a.steps, a.wte, a.wpe, a.ids,
-                     a.logprob, a.x, a.pos_base);
+  hipLaunchKernelGGL(k_dec_select<RAG>, dim3(a.N), dim3(256), 0, s, a.logits, nblk, a.N, a.E, step, a.steps, a.wte, a.wpe, a.ids,
+                     a.logprob, a.x, a.pos_base, plen);
   return hipGetLastError();
 }
 
@@ -2114,7 +2188,8 @@ static hipError_t dec_prefill_layers(const DecoderArgs& a, int n0, int gN, int P
                                      a.eps, nullptr, nullptr, s)));
     }
     hipLaunchKernelGGL(k_kv_append, dim3(gN, P), dim3(192), 0, s, a.pre_qkv, kc, vc, P, a.max_steps, E);
-    hipLaunchKernelGGL(k_dec_attention, dim3(gN * a.heads, P), dim3(256), 0, s, a.pre_qkv, kc, vc, E, a.heads, 0, a.max_steps, a.pre_att, P);
+    hipLaunchKernelGGL((k_dec_attention<false, 0>), dim3(gN * a.heads, P), dim3(256), 0, s, a.pre_qkv, kc, vc, E, a.heads, 0, a.max_steps, a.pre_att, P,
+                       nullptr, 0);
     for (int r0 = 0; r0 < R; r0 += 128) {
       const int rows = R - r0 < 128 ? R - r0 : 128;
       PIO_TRY((dec_gemm<DE_RESID, 0>(w.proj_w, a.pre_att + (size_t)r0 * E, rows, E, E, w.proj_b, a.pre_x + (size_t)r0 * E, nullptr, nullptr, 0.f,
@@ -2154,6 +2229,100 @@ hipError_t launch_decode_prompted(const DecoderArgs& a, const float* prompt, int
   for (int step = 0; step < a.steps; ++step) {
     PIO_TRY(dec_head_step(a, step, filtered, s));            // -> ids[.][step], x = wte[id] + wpe[P + step]
     if (step + 1 < a.steps) PIO_TRY(dec_layers_step(a, P + step, s));
+  }
+  return hipGetLastError();
+}
+
+// ---- ragged prompted decode: prefix n has its own prompt length P_n = plen[n] (device memory, 1 <= P_n <= Pmax).  Everything the
+// host sees is (N, Pmax, steps), so one captured graph serves any mix of lengths.  The prompt rows are laid out at Pmax per prefix
+// (positions >= P_n: zeros, k_build_prompt_ragged) and prefilled like a uniform prompt of Pmax positions: causal attention keeps
+// positions >= P_n out of every position < P_n, and their keys / values (slots P_n .. Pmax - 1) are rewritten by decode step k at slot
+// P_n + k before any later step reads that slot (step k attends over slots 0 .. P_n + k, the last one being its own fresh key).  The
+// input of the first step is the prefill output of position P_n - 1; step k runs position P_n + k (k_dec_attention<true>) and the
+// head writes x = wte[id] + wpe[P_n + k] (k_dec_select*<true>).  The head is the uniform path's; the GEMMs: see launch_decode_prompted_ragged.
+// Pass `cls` of the ragged prefill writes keys / values (and the first step's input) only for its own prefixes: MASK 1 = plen[n] <= split
+// (family A), 2 = plen[n] > split (family B).
+template <int MASK>
+__global__ __launch_bounds__(192) void k_kv_append_masked(const float* __restrict__ qkv, float* kcache, float* vcache, int P, int max_steps, int E,
+                                                          const int32_t* __restrict__ plen, int split) {
+  const int n = blockIdx.x, p = blockIdx.y;
+  if ((plen[n] <= split) != (MASK == 1)) return;          // block-uniform
+  const float4* src = (const float4*)(qkv + ((size_t)n * P + p) * 3 * E);
+  float4* kc = (float4*)(kcache + ((size_t)n * max_steps + p) * E);
+  float4* vc = (float4*)(vcache + ((size_t)n * max_steps + p) * E);
+  for (int d = threadIdx.x; d < E / 4; d += 192) { kc[d] = src[E / 4 + d]; vc[d] = src[E / 2 + d]; }
+}
+template <int MASK>
+__global__ __launch_bounds__(256) void k_dec_last_rows_ragged(const float* __restrict__ xp, int Pmax, const int32_t* __restrict__ plen, int split,
+                                                              int E, float* x) {
+  const int n = blockIdx.x;
+  if ((plen[n] <= split) != (MASK == 1)) return;
+  const size_t r = (size_t)n * Pmax + plen[n] - 1;
+  for (int d = threadIdx.x; d < E; d += 256) x[(size_t)n * E + d] = xp[r * E + d];
+}
+// dec_prefill_layers on one GEMM family (dec_gemm_cls), keys / values kept for the prefixes of that family only
+template <int MASK>
+static hipError_t dec_prefill_layers_masked(const DecoderArgs& a, int n0, int gN, int P, const int32_t* plen, int split, hipStream_t s) {
+  const int E = a.E, R = gN * P, cls = MASK == 1 ? DEC_CLS_A : DEC_CLS_B;
+  for (int l = 0; l < a.layers; ++l) {
+    const DecLayerW& w = a.layer[l];
+    float* kc = a.kcache + ((size_t)l * a.N + n0) * a.max_steps * E;
+    float* vc = a.vcache + ((size_t)l * a.N + n0) * a.max_steps * E;
+    for (int r0 = 0; r0 < R; r0 += 128) {
+      const int rows = R - r0 < 128 ? R - r0 : 128;
+      PIO_TRY((dec_gemm_cls<DE_STORE, 1>(cls, w.attn_w, a.pre_x + (size_t)r0 * E, rows, 3 * E, E, w.attn_d, a.pre_qkv + (size_t)r0 * 3 * E, w.attn_c,
+                                         a.eps, nullptr, nullptr, s)));
+    }
+    hipLaunchKernelGGL(k_kv_append_masked<MASK>, dim3(gN, P), dim3(192), 0, s, a.pre_qkv, kc, vc, P, a.max_steps, E, plen, split);
+    hipLaunchKernelGGL((k_dec_attention<false, MASK>), dim3(gN * a.heads, P), dim3(256), 0, s, a.pre_qkv, kc, vc, E, a.heads, 0, a.max_steps, a.pre_att,
+                       P, plen, split);
+    for (int r0 = 0; r0 < R; r0 += 128) {
+      const int rows = R - r0 < 128 ? R - r0 : 128;
+      PIO_TRY((dec_gemm_cls<DE_RESID, 0>(cls, w.proj_w, a.pre_att + (size_t)r0 * E, rows, E, E, w.proj_b, a.pre_x + (size_t)r0 * E, nullptr, 0.f,
+                                         nullptr, nullptr, s)));
+    }
+    for (int r0 = 0; r0 < R; r0 += 128) {
+      const int rows = R - r0 < 128 ? R - r0 : 128;
+      PIO_TRY((dec_gemm_cls<DE_GELU, 1>(cls, w.fc_w, a.pre_x + (size_t)r0 * E, rows, 4 * E, E, w.fc_d, a.pre_hid + (size_t)r0 * 4 * E, w.fc_c, a.eps,
+                                        nullptr, nullptr, s)));
+    }
+    for (int r0 = 0; r0 < R; r0 += 128) {
+      const int rows = R - r0 < 128 ? R - r0 : 128;
+      PIO_TRY((dec_gemm_cls<DE_RESID, 0>(cls, w.fc2_w, a.pre_hid + (size_t)r0 * 4 * E, rows, E, 4 * E, w.fc2_b, a.pre_x + (size_t)r0 * E, nullptr, 0.f,
+                                         a.splitk_ws, a.splitk_cnt, s)));
+    }
+  }
+  return hipGetLastError();
+}
+
+template <int MASK>
+static hipError_t dec_prefill_ragged_pass(const DecoderArgs& a, const float* prompt, int Pmax, const int32_t* plen, int split, hipStream_t s) {
+  const int gmax = a.pre_rows / Pmax;
+  for (int n0 = 0; n0 < a.N; n0 += gmax) {
+    const int gN = a.N - n0 < gmax ? a.N - n0 : gmax;
+    hipLaunchKernelGGL(k_dec_prompt_x_all, dim3(gN, Pmax), dim3(256), 0, s, prompt + (size_t)n0 * Pmax * a.E, a.wpe, Pmax, a.E, a.pre_x);
+    PIO_TRY(dec_prefill_layers_masked<MASK>(a, n0, gN, Pmax, plen + n0, split, s));
+    hipLaunchKernelGGL(k_dec_last_rows_ragged<MASK>, dim3(gN), dim3(256), 0, s, a.pre_x, Pmax, plen + n0, split, a.E, a.x + (size_t)n0 * a.E);
+  }
+  return hipGetLastError();
+}
+
+// Bits: row n gets the ids pio_viecap_decode gives for that row alone with P = P_n.  That decode runs its prompt through the batched prefill
+// on k_dec_gemm (P_n <= 16 prompt rows: one row group) or k_dec_gemm_b (17 .. 128), position by position (family A) when the batched
+// prefill is off, and its steps on k_dec_gemm (one row).  So the prefill runs twice, on family A for the prefixes with P_n <= split and on
+// family B for the others (split = 16; 256 when the uniform path would not batch its prefill), each pass keeping only its own prefixes'
+// keys / values and first input, and every step on family A (dec_gemm_cls: a row's sums do not depend on the launch).  The second pass is
+// skipped when Pmax <= split.  Attention per row is the uniform kernel at that row's key count; the head gives the exact fp32 head's ids.
+hipError_t launch_decode_prompted_ragged(const DecoderArgs& a, const float* prompt, int Pmax, const int32_t* plen, int split, hipStream_t s) {
+  const bool filtered = PIO_LMHEAD_FILTER && a.logprob == nullptr && a.head_w16 != nullptr;
+  if (Pmax < 1 || Pmax > 128 || a.steps < 1 || plen == nullptr || a.lm_tail || a.pre_x == nullptr || Pmax > a.pre_rows || a.N > 128 ||
+      !dec_args_ok(a, filtered, Pmax + a.steps - 1))
+    return hipErrorInvalidValue;
+  PIO_TRY(dec_prefill_ragged_pass<1>(a, prompt, Pmax, plen, split, s));
+  if (Pmax > split) PIO_TRY(dec_prefill_ragged_pass<2>(a, prompt, Pmax, plen, split, s));
+  for (int step = 0; step < a.steps; ++step) {
+    PIO_TRY(dec_head_step<true>(a, step, filtered, s, plen));          // -> ids[.][step], x = wte[id] + wpe[P_n + step]
+    if (step + 1 < a.steps) PIO_TRY(dec_layers_step<true>(a, step, s, plen));
   }
   return hipGetLastError();
 }

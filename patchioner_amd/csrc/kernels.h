@@ -230,6 +230,11 @@ struct DecoderArgs {
 hipError_t launch_decode_greedy(const DecoderArgs& a, hipStream_t s);
 // ViECap greedy search: prompt [N][P][E] at positions 0..P-1, then a.steps greedy tokens (a.pos_base = P - 1)
 hipError_t launch_decode_prompted(const DecoderArgs& a, const float* prompt, int P, hipStream_t s);
+// the same with a prompt length per prefix: prompt [N][Pmax][E] (k_build_prompt_ragged), plen [N] on the device (1 <= plen[n] <= Pmax <= 128,
+// N <= 128); the batched prefill workspace is required (a.pre_x), the ticketed LM-head tail (a.lm_tail) is refused; a.pos_base is not read.
+// split: prefixes with plen[n] <= split are prefilled on the GEMM family of a one-row-group prefill, the others on the tiled one (16; 256 when
+// the uniform decode would take its prompt position by position) -- row n then has the ids of launch_decode_prompted on that row alone
+hipError_t launch_decode_prompted_ragged(const DecoderArgs& a, const float* prompt, int Pmax, const int32_t* plen, int split, hipStream_t s);
 // teacher-forced pass over given tokens [N][Lmax] (rows of lens[n] tokens): nll[n] = sum over p + 1 < lens[n] of -log p(token p+1 | tokens <= p); N <= 64
 hipError_t launch_lm_score(const DecoderArgs& a, const int32_t* tokens, const int32_t* lens, int Lmax, float* nll, hipStream_t s);
 // beam search building blocks (N <= 16 beams per call; stats: [N][2] scratch; logp [N][V] = log softmax of the next-token logits)
@@ -261,6 +266,19 @@ hipError_t launch_sgemm_tn(const float* A, int lda, const float* W, int ldw, con
 hipError_t launch_activation_f32(float* y, size_t n, int act, hipStream_t s);     // 2 tanh, 3 sigmoid, in place
 hipError_t launch_build_prompt(const float* cont, const int32_t* tokens, const float* wte, int N, int Lc, int Lt, int E, int V,
                                int soft_first, float* prompt, hipStream_t s);
+// hard prompt on the device (viecap.hip): top-k entities of probs [N][K] -> token rows [N][Lmax] padded per call (seg[n] = call of row n,
+// NULL: one call) -> lens[n] = the call's longest row.  frag_off / frag_len [2K]: middle (2e) and last (2e + 1) fragment of entity e in frag_ids
+struct ComposeArgs {
+  const float* probs; int N, K;
+  const int32_t *frag_ids, *frag_off, *frag_len;
+  int head_off, head_len, empty_off, empty_len;
+  int top_k; float threshold; int pad_id; const int32_t* seg; int Lmax;
+  int32_t *tokens, *lens, *rawlen;                // rawlen [N]: scratch
+};
+hipError_t launch_compose_prompts(const ComposeArgs& a, hipStream_t s);
+// prompt [N][Lc + Ltmax][E] with row n's hard prompt lt[n] tokens long (positions past Lc + lt[n]: zeros); plen[n] = Lc + lt[n]
+hipError_t launch_build_prompt_ragged(const float* cont, const int32_t* tokens, const int32_t* lt, const float* wte, int N, int Lc, int Ltmax,
+                                      int E, int V, int soft_first, float* prompt, int32_t* plen, hipStream_t s);
 hipError_t launch_l2norm_rows(float* x, int N, int D, hipStream_t s);
 // ---- preprocess.hip: image_transforms on the device (P/src/model.py:347-357; Pillow's 8-bit two-pass resampler) ----
 struct PrepImage {

@@ -230,4 +230,142 @@ hipError_t launch_build_prompt(const float* cont, const int32_t* tokens, const f
   return hipGetLastError();
 }
 
+// ---- hard prompt on the device (pipelined head): top-k entities -> token row -> per-call padding ----------------------------
+// The prompt "There are e1, e2, ..., ek in image." (compose_discrete_prompts, P/src/viecap/utils.py:55-74) tokenises as the concatenation
+// head + middle(e1) + ... + middle(e_{k-1}) + last(e_k) of fragments the host tokenised once and CHECKED against the whole string
+// (viecap.PromptFragments); no entity above the threshold: the whole "There are something in image." row.
+// Selection order = torch.topk's on the probabilities: larger first; equal values by the LOWER index (torch.topk leaves the order of exact
+// ties unspecified; this is the order fixed here); NaN above every number (torch's ordering of NaN); cut at the first value < threshold
+// (retrieval_categories.py:97-116; a NaN is not below it).
+__device__ __forceinline__ bool vc_topk_before(float v, int i, float w, int j) {
+  const bool vn = v != v, wn = w != w;
+  if (vn != wn) return vn;
+  if (!vn && v != w) return v > w;
+  return i < j;
+}
+
+// one workgroup per row; top_k <= 8 arg-max passes, each over the entities that come AFTER the previous pick in that order
+__global__ __launch_bounds__(256) void k_compose_prompts(const float* __restrict__ probs, int K, const int32_t* __restrict__ frag_ids,
+                                                         const int32_t* __restrict__ frag_off, const int32_t* __restrict__ frag_len, int head_off,
+                                                         int head_len, int empty_off, int empty_len, int top_k, float threshold, int Lmax,
+                                                         int32_t* tokens, int32_t* rawlen) {
+  __shared__ float s_v[4];
+  __shared__ int s_i[4];
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const float* p = probs + (size_t)n * K;
+  int picks[8];
+  int cnt = 0;
+  float pv = 0.f;
+  int pi = -1;                                     // previous pick (-1: none yet)
+  const int passes = top_k < K ? top_k : K;
+  for (int r = 0; r < 8; ++r) {
+    if (r >= passes) break;
+    float bv = 0.f;
+    int bi = -1;
+    for (int i = tid; i < K; i += 256) {
+      const float v = p[i];
+      if (pi >= 0 && !vc_topk_before(pv, pi, v, i)) continue;           // already picked (or ordered before a pick)
+      if (bi < 0 || vc_topk_before(v, i, bv, bi)) { bv = v; bi = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o);
+      const int oi = __shfl_xor(bi, o);
+      if (oi >= 0 && (bi < 0 || vc_topk_before(ov, oi, bv, bi))) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { s_v[wid] = bv; s_i[wid] = bi; }
+    __syncthreads();
+    bv = s_v[0]; bi = s_i[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+      if (s_i[w] >= 0 && (bi < 0 || vc_topk_before(s_v[w], s_i[w], bv, bi))) { bv = s_v[w]; bi = s_i[w]; }
+    __syncthreads();                               // s_v / s_i are rewritten by the next pass
+    if (bi < 0 || bv < threshold) break;           // block-uniform
+    picks[r] = bi;
+    cnt = r + 1;
+    pv = bv; pi = bi;
+  }
+  int32_t* row = tokens + (size_t)n * Lmax;
+  int o = 0;
+  auto put = [&](int off, int len) {
+    for (int d = tid; d < len; d += 256)
+      if (o + d < Lmax) row[o + d] = frag_ids[off + d];
+    o += len;
+  };
+  if (cnt == 0) {
+    put(empty_off, empty_len);
+  } else {
+    put(head_off, head_len);
+    for (int r = 0; r < 8; ++r) {
+      if (r >= cnt) break;
+      const int f = 2 * picks[r] + (r + 1 == cnt ? 1 : 0);                  // middle fragment, or the last one
+      put(frag_off[f], frag_len[f]);
+    }
+  }
+  if (tid == 0) rawlen[n] = o < Lmax ? o : Lmax;
+}
+
+// pad_sequence(batch_first=True, padding_value=pad_id) per caption call: seg[n] = call of row n (NULL: one call); lens[n] = the call's
+// longest row, the hard-prompt length the reference feeds the language model for row n
+__global__ __launch_bounds__(256) void k_pad_prompts(const int32_t* __restrict__ rawlen, const int32_t* __restrict__ seg, int N, int Lmax,
+                                                     int pad_id, int32_t* tokens, int32_t* lens) {
+  __shared__ int s_m[4];
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int my = seg ? seg[n] : 0;
+  int m = 0;
+  for (int r = tid; r < N; r += 256)
+    if ((seg ? seg[r] : 0) == my) m = max(m, rawlen[r]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
+  if (lane == 0) s_m[wid] = m;
+  __syncthreads();
+  m = max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3]));
+  for (int d = rawlen[n] + tid; d < Lmax; d += 256) tokens[(size_t)n * Lmax + d] = pad_id;
+  if (tid == 0) lens[n] = m;
+}
+
+hipError_t launch_compose_prompts(const ComposeArgs& a, hipStream_t s) {
+  if (a.N < 1 || a.K < 1 || a.top_k < 1 || a.top_k > 8 || a.Lmax < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_compose_prompts, dim3(a.N), dim3(256), 0, s, a.probs, a.K, a.frag_ids, a.frag_off, a.frag_len, a.head_off, a.head_len,
+                     a.empty_off, a.empty_len, a.top_k, a.threshold, a.Lmax, a.tokens, a.rawlen);
+  hipLaunchKernelGGL(k_pad_prompts, dim3(a.N), dim3(256), 0, s, a.rawlen, a.seg, a.N, a.Lmax, a.pad_id, a.tokens, a.lens);
+  return hipGetLastError();
+}
+
+// Ragged k_build_prompt: row n's hard prompt has lt[n] tokens (0 <= lt[n] <= Ltmax; lt NULL: none), so its prompt is P_n = Lc + lt[n]
+// positions, laid out from position 0 in the order k_build_prompt uses (soft first or hard first); positions P_n .. Pmax - 1 are zeros.
+// plen[n] = P_n (at least 1) is what the ragged decode reads.
+__global__ __launch_bounds__(256) void k_build_prompt_ragged(const float* __restrict__ cont, const int32_t* __restrict__ tokens,
+                                                             const int32_t* __restrict__ lt, const float* __restrict__ wte, int Lc, int Ltmax,
+                                                             int E, int V, int soft_first, float* prompt, int32_t* plen) {
+  const int n = blockIdx.y, p = blockIdx.x, Pmax = Lc + Ltmax;
+  int Lt = lt ? lt[n] : 0;
+  Lt = Lt < 0 ? 0 : (Lt > Ltmax ? Ltmax : Lt);
+  if (Lc + Lt < 1) Lt = 1;                         // no soft prompt and an empty row: one pad position (the API refuses Ltmax < 1 then)
+  const int P = Lc + Lt;
+  if (p == 0 && threadIdx.x == 0) plen[n] = P;
+  float* dst = prompt + ((size_t)n * Pmax + p) * E;
+  if (p >= P) {
+    for (int d = threadIdx.x; d < E; d += 256) dst[d] = 0.f;
+    return;
+  }
+  const bool soft = soft_first ? p < Lc : p >= Lt;
+  const float* src;
+  if (soft) {
+    src = cont + ((size_t)n * Lc + (soft_first ? p : p - Lt)) * E;
+  } else {
+    int id = tokens[(size_t)n * Ltmax + (soft_first ? p - Lc : p)];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    src = wte + (size_t)id * E;
+  }
+  for (int d = threadIdx.x; d < E; d += 256) dst[d] = src[d];
+}
+
+hipError_t launch_build_prompt_ragged(const float* cont, const int32_t* tokens, const int32_t* lt, const float* wte, int N, int Lc, int Ltmax,
+                                      int E, int V, int soft_first, float* prompt, int32_t* plen, hipStream_t s) {
+  if (N < 1 || Lc + Ltmax < 1 || Lc < 0 || Ltmax < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_build_prompt_ragged, dim3(Lc + Ltmax, N), dim3(256), 0, s, cont, tokens, lt, wte, Lc, Ltmax, E, V, soft_first, prompt, plen);
+  return hipGetLastError();
+}
+
 }  // namespace pio

@@ -418,6 +418,47 @@ class Engine:
                                              e - s, Lt, 1 if soft_first else 0, int(steps), ptr(ids[s:e]), _stream()))
         return ids
 
+    def viecap_compose_prompts(self, probs: torch.Tensor, frag, top_k: int, threshold: float, pad_id: int,
+                               seg: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The hard prompt on the device (pio_viecap_compose_prompts): probs [N, K] (viecap_entity_logits), ``frag`` a
+        viecap.PromptFragments on this device, ``seg`` [N] int32 caption call of every row (None: one call) -> token rows
+        [N, frag.Lmax] int32 padded with ``pad_id`` and the per-row hard-prompt length [N] int32 (the call's longest row)."""
+        assert probs.is_cuda and probs.dtype == torch.float32 and probs.is_contiguous()
+        N, K = int(probs.shape[0]), int(probs.shape[1])
+        if 2 * K != int(frag.off.numel()):
+            raise ValueError("viecap_compose_prompts: %d entity probabilities per row, the fragment table has %d entities" % (K, frag.off.numel() // 2))
+        if not 1 <= int(top_k) <= frag.top_k:
+            raise ValueError("viecap_compose_prompts: top_k %d outside 1..%d, the table's bound (its Lmax holds %d entities)" % (top_k, frag.top_k, frag.top_k))
+        tokens = torch.empty(N, frag.Lmax, device=self.device, dtype=torch.int32)
+        lens = torch.empty(N, device=self.device, dtype=torch.int32)
+        scratch = torch.empty(N, device=self.device, dtype=torch.int32)
+        check(self.lib.pio_viecap_compose_prompts(self.h, ptr(probs), N, K, ptr(frag.ids), ptr(frag.off), ptr(frag.length), frag.head_off,
+                                                  frag.head_len, frag.empty_off, frag.empty_len, int(top_k), float(threshold), int(pad_id),
+                                                  ptr(seg) if seg is not None else None, frag.Lmax, ptr(tokens), ptr(lens), ptr(scratch),
+                                                  _stream()))
+        return tokens, lens
+
+    def viecap_decode_ragged(self, cont: Optional[torch.Tensor], tokens: Optional[torch.Tensor], lens: Optional[torch.Tensor],
+                             soft_first: bool = True, steps: int = 64) -> torch.Tensor:
+        """viecap_decode with a hard-prompt length per row (pio_viecap_decode_ragged): cont [N, Lc, E] device or None (only_hard_prompt),
+        tokens [N, Ltmax] int32 device, lens [N] int32 device (row n uses tokens[n, :lens[n]]), both None without a hard prompt ->
+        greedy ids [N, steps] int32; row n's ids are those of viecap_decode on that row alone with its own lens[n] tokens."""
+        if cont is None and tokens is None:
+            raise ValueError("viecap_decode_ragged: neither a soft prompt nor prompt tokens")
+        if (tokens is None) != (lens is None):
+            raise ValueError("viecap_decode_ragged: tokens and lens go together")
+        N = int(cont.shape[0] if cont is not None else tokens.shape[0])
+        Lt = int(tokens.shape[1]) if tokens is not None else 0
+        ids = torch.empty(N, steps, device=self.device, dtype=torch.int32)
+        cap = min(self.max_prefixes, 128)                 # rows of one ragged decode
+        for s in range(0, N, cap):
+            e = min(N, s + cap)
+            check(self.lib.pio_viecap_decode_ragged(self.h, ptr(cont[s:e].contiguous()) if cont is not None else None,
+                                                    ptr(tokens[s:e].contiguous()) if tokens is not None else None,
+                                                    ptr(lens[s:e].contiguous()) if lens is not None else None,
+                                                    e - s, Lt, 1 if soft_first else 0, int(steps), ptr(ids[s:e]), _stream()))
+        return ids
+
     def viecap_build_prompt(self, cont: Optional[torch.Tensor], tokens: Optional[torch.Tensor], soft_first: bool = True) -> torch.Tensor:
         """The prompt embeddings [N, Lc + Lt, E] as viecap_decode assembles them (word_embed + torch.cat, entrypoint.py:126-135)."""
         tok = self._dev(tokens, torch.int32) if tokens is not None else None
@@ -478,7 +519,8 @@ class Engine:
 
 
 class DecoderClone:
-    """Handle from pio_clone_decoder: borrows the parent's decoder weights, owns its workspaces.  Only decode_greedy."""
+    """Handle from pio_clone_decoder: borrows the parent's decoder weights, owns its workspaces.  decode_greedy and viecap_decode_ragged
+    (the soft prompt and the token rows come from the parent: the mapping network and the entity table stay on it)."""
 
     def __init__(self, parent: Engine):
         self.lib, self.parent, self.device = parent.lib, parent, parent.device
@@ -500,3 +542,4 @@ class DecoderClone:
 
     _dev = Engine._dev
     decode_greedy = Engine.decode_greedy
+    viecap_decode_ragged = Engine.viecap_decode_ragged

@@ -670,6 +670,13 @@ class Patchioner(nn.Module):
         if self.viecap is not None:
             if return_n_best_sims:
                 raise Exception("return_n_best_sims is not supported with viecap")
+            if self._defer and self.viecap.args.using_greedy_search:
+                # forward_async: mapping, entity probabilities, hard prompt and the ragged decode are enqueued; ids -> text in result()
+                if compute_scores:
+                    raise NotImplementedError("forward_async does not defer score lists; call forward() for compute_scores")
+                ids = self.viecap.enqueue(dino_tokens)
+                self.last_ids = ids
+                return _PendingVieCapCaptions(ids, self.viecap)
             out = self.viecap.forward(dino_tokens, compute_scores=compute_scores)
             self.last_ids = self.viecap.last_ids      # [N, 64] ids of the greedy search: what dist.sharded_* gathers
             return out
@@ -754,6 +761,17 @@ class _PendingCaptions:
 
     def resolve(self):
         return self.tokenizer.batch_captions(self.ids_host.tolist(), decoding_method=self.decoding_method)
+
+
+class _PendingVieCapCaptions(_PendingCaptions):
+    """Greedy ids of the ViECap head still on the device; resolved as VieCapHead.forward would return them (a single row: a str)."""
+
+    def __init__(self, ids_dev, head):
+        super().__init__(ids_dev, None, None)
+        self.head = head
+
+    def resolve(self):
+        return self.head.captions(self.ids_host.tolist())
 
 
 class PendingForward:

@@ -60,8 +60,17 @@ def _rows_of(imgs, regions) -> int:
 
 
 class _Group:
-    def __init__(self, cap: int, dim: int, steps: int, device):
-        self.prefix = torch.empty(cap, dim, device=device, dtype=torch.float32)
+    def __init__(self, cap: int, dim: int, steps: int, device, viecap_shape=None):
+        # viecap_shape (Lc, Lmax, E): a ViECap head's soft prompts [cap, Lc, E], hard-prompt token rows [cap, Lmax] and their lengths
+        self.prefix = torch.empty(cap, dim if viecap_shape is None else 1, device=device, dtype=torch.float32)
+        self.cont = self.tokens = self.lens = None
+        if viecap_shape is not None:
+            Lc, Lmax, E = viecap_shape
+            if Lc:
+                self.cont = torch.empty(cap, Lc, E, device=device, dtype=torch.float32)
+            if Lmax:
+                self.tokens = torch.empty(cap, Lmax, device=device, dtype=torch.int32)
+                self.lens = torch.empty(cap, device=device, dtype=torch.int32)
         self.ids_host = torch.empty(cap, steps, dtype=torch.int32).pin_memory()
         self.ids_dev: Optional[torch.Tensor] = None
         self.counts: List[int] = []
@@ -76,7 +85,14 @@ class _Group:
 class TraceCaptionPipeline:
     """``for captions in TraceCaptionPipeline(model).run(batches)`` with batches = iterable of (imgs, regions): ``regions`` = the
     traces of the batch (caption_from=patches), ``None`` (the CLS token, caption_from=cls) or a ``BoxRegions`` (dense / region
-    captioning: [B][NB] captions per batch).  ``RegionCaptionPipeline`` is the same class under the name that fits boxes."""
+    captioning: [B][NB] captions per batch).  ``RegionCaptionPipeline`` is the same class under the name that fits boxes.
+
+    A model with a ViECap head (greedy search) is pipelined too: stage 1 runs the mapping network, the entity probabilities and the
+    hard prompt composed on the device (each batch is one caption call, padded to its own longest prompt), stage 2 ONE ragged decode
+    of ``viecap`` 64 steps for the group, every row at its own prompt length.  Captions come back per batch exactly as ``forward``
+    returns them.  Beam search raises ValueError, ``BoxRegions`` NotImplementedError."""
+
+    viecap = None                         # the model's ViECap head, if it has one (set in __init__)
 
     def __init__(self, model, group_batches: int = 4, use_attention_tracing: bool = False, steps: int = 30,
                  stage_replicas: Sequence = (), stage_cus: Optional[int] = None, decode_cus: Optional[int] = None,
@@ -86,6 +102,13 @@ class TraceCaptionPipeline:
         so that one batch's GEMM tails, epilogues and launch gaps are filled by the other's kernels."""
         self.m, self.eng = model, model.engine
         self.stage_models = [model] + list(stage_replicas)
+        self.viecap = getattr(model, "viecap", None)
+        viecap_shape = None
+        if self.viecap is not None:
+            for sm in self.stage_models:
+                sm.viecap.check_device_path()      # beam search / a hard prompt that does not decompose: ValueError
+            steps = self.viecap.steps              # greedy_search's 64 steps, whatever the DeCap default says
+            viecap_shape = self.viecap.prompt_shape() + (int(self.eng.cfg.dec_embd),)
         # ``decode_replicas``: further instances (same weights, own decoder workspace) so that consecutive groups'
         # decodes run concurrently, each on its own stream: a decode is a chain of ~660 small dependent kernels that
         # stretches 2x when it shares the chip with stage 1, and two chains in flight hide each other's waits.
@@ -128,7 +151,7 @@ class TraceCaptionPipeline:
         self._ndecoded = 0
         self._nstaged = 0
         cap = self.eng.max_prefixes
-        self.groups = [_Group(cap, self.eng.prefix_size, steps, self.eng.device) for _ in range(1 + len(self.decode_engines))]
+        self.groups = [_Group(cap, self.eng.prefix_size, steps, self.eng.device, viecap_shape) for _ in range(1 + len(self.decode_engines))]
         self.last_ids: Optional[torch.Tensor] = None
 
     def _concurrent_streams(self, n: int, priority: int = 0, candidates: int = 16, beside: Sequence = ()) -> List[torch.cuda.Stream]:
@@ -273,6 +296,23 @@ class TraceCaptionPipeline:
                         grids = self_attn * grids
                     emb = eng.region_reduce(tokens, grids, None, 1.0 / m.num_patch_tokens)
                 s += n
+                if self.viecap is not None:
+                    # caption_tokens hands the raw region features to the ViECap head (no bank projection): mapping network, entity
+                    # probabilities and this batch's hard prompts (one caption call) straight into the group's buffers
+                    cont, tok, lens = m.viecap.stage(emb)
+                    r0 = g.rows
+                    if g.cont is not None:
+                        g.cont[r0:r0 + n].copy_(cont)
+                    if g.tokens is not None:
+                        g.tokens[r0:r0 + n].copy_(tok)
+                        g.lens[r0:r0 + n].copy_(lens)
+                    g.rows += n
+                    g.flushed += n
+                    g.counts.append((n, None))
+                    ev = torch.cuda.Event()
+                    ev.record(stream)
+                    g.staged.append(ev)
+                    continue
                 g.rows += n
                 g.counts.append((n, None))
                 g.pending.append((emb, stream, m))
@@ -314,7 +354,13 @@ class TraceCaptionPipeline:
             for ev in g.staged:
                 sb.wait_event(ev)
             g.staged = []
-            ids, _ = eng.decode_greedy(g.prefix[:g.rows], steps=self.steps)
+            if self.viecap is not None:
+                ids = eng.viecap_decode_ragged(g.cont[:g.rows] if g.cont is not None else None,
+                                               g.tokens[:g.rows] if g.tokens is not None else None,
+                                               g.lens[:g.rows] if g.lens is not None else None,
+                                               soft_first=self.viecap.soft_first(), steps=self.steps)
+            else:
+                ids, _ = eng.decode_greedy(g.prefix[:g.rows], steps=self.steps)
             g.ids_dev = ids
             g.ids_host[:g.rows].copy_(ids, non_blocking=True)
             g.decoded.record(sb)
@@ -327,6 +373,10 @@ class TraceCaptionPipeline:
         out, s = [], 0
         for n, nb in g.counts:
             k = n if nb is None else n * nb
+            if self.viecap is not None:                    # as VieCapHead.forward returns them (a batch of one: a str)
+                out.append(self.viecap.captions(rows[s:s + k]))
+                s += k
+                continue
             caps = self.m.tokenizer.batch_captions(rows[s:s + k], decoding_method=self.m.decoding_method)
             if nb is not None and caps is not None:        # [B][NB], as forward()'s bbox_capts (model.py:1037-1041)
                 caps = [caps[i * nb:(i + 1) * nb] for i in range(n)]
@@ -401,6 +451,8 @@ class TraceCaptionPipeline:
 
         aligned = self.vit_batches <= self.group_batches and self.group_batches % self.vit_batches == 0
         for imgs, traces in batches:
+            if self.viecap is not None and isinstance(traces, BoxRegions):
+                raise NotImplementedError("TraceCaptionPipeline: boxes with a ViECap head are not pipelined; call forward(bboxes=...)")
             g = self.groups[cur]
             n = _rows_of(imgs, traces)
             if n > g.prefix.shape[0]:

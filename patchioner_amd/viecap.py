@@ -4,7 +4,9 @@
 numerical is a C-ABI call (mapping network, entity logits, prompt assembly, KV-cached greedy search: viecap.hip /
 decoder.hip); what stays on the host is what is host work in the reference too: top-k / threshold over the 80-odd entity
 probabilities, composing the hard-prompt STRING, tokenising it, cutting the generated ids at the first full stop and
-detokenising.
+detokenising.  ``VieCapHead.enqueue`` (forward_async, the pipeline) moves the hard prompt to the device as well
+(``PromptFragments``: the prompt as pre-tokenised fragments, checked against the tokenizer; ``pio_viecap_compose_prompts``) and
+decodes every row at its own prompt length (``pio_viecap_decode_ragged``).
 
 There is no network on the target, so nothing is fetched from the HuggingFace hub: the GPT-2 tokenizer comes from local
 ``vocab.json`` / ``merges.txt`` (``viecap.tokenizer_path``) or an object with ``encode`` / ``decode`` / ``pad_token_id``
@@ -123,6 +125,77 @@ def top_k_entities(texts: Sequence[str], probs_row: Sequence[float], top_k: int,
     return out
 
 
+class PromptFragments:
+    """The hard prompt as a concatenation of pre-tokenised fragments, for composing it on the device (viecap.hip: k_compose_prompts).
+
+    GPT-2's byte-level BPE splits text into pre-tokens before merging, and the text before each ``" e_i"`` of
+    ``"There are e1, e2, ..., ek in image."`` ends a pre-token (``"are"`` or ``","``, then a space).  So the ids of the whole prompt are
+    ``enc("There are")`` + ``enc(" e,")`` for every entity but the last + ``enc(" e in image.")`` for the last; with no entity, the whole
+    ``enc("There are something in image.")``.  The tokenizer may be any object with ``encode``, so this is CHECKED at construction, not
+    assumed: every entity alone, first, middle and last (``[e]``, ``[e, e]``, ``[e, e, e]``) against ``encode`` of the whole string, and
+    the empty prompt.  ``bad`` lists the entities whose prompts do not decompose; ``check()`` raises naming them (the host path,
+    ``VieCapHead.forward``, does not use the table and keeps working).
+
+    ``ids`` = head, then the empty row, then per entity its middle and last fragment; ``off`` / ``length`` [2K] (2e: middle, 2e + 1: last);
+    ``Lmax`` = the longest possible row: head + (top_k - 1) x longest middle + longest last, or the empty row if that is longer."""
+
+    def __init__(self, tokenizer, entities: Sequence[str], top_k: int):
+        enc = tokenizer.encode
+        head = [int(t) for t in enc("There are")]
+        empty = [int(t) for t in enc(compose_discrete_prompt_text([]))]
+        mids, lasts, bad = [], [], []
+        for e in entities:
+            m, l = [int(t) for t in enc(" " + e + ",")], [int(t) for t in enc(" " + e + " in image.")]
+            mids.append(m)
+            lasts.append(l)
+            for k in (1, 2, 3):       # e alone (first and last), first of two, in the middle of three (its neighbours: e itself)
+                if list(enc(compose_discrete_prompt_text([e] * k))) != head + m * (k - 1) + l:
+                    bad.append(e)
+                    break
+        self.bad = bad
+        self.empty_ok = list(enc(compose_discrete_prompt_text([]))) == empty
+        self.top_k = int(top_k)
+        ids = head + empty
+        off, length = [], []
+        for m, l in zip(mids, lasts):
+            off += [len(ids), len(ids) + len(m)]
+            length += [len(m), len(l)]
+            ids += m + l
+        self.ids = torch.tensor(ids, dtype=torch.int32)
+        self.off = torch.tensor(off, dtype=torch.int32)
+        self.length = torch.tensor(length, dtype=torch.int32)
+        self.off_host, self.length_host = self.off.tolist(), self.length.tolist()
+        self.head_off, self.head_len = 0, len(head)
+        self.empty_off, self.empty_len = len(head), len(empty)
+        k = max(1, min(self.top_k, len(entities)))
+        longest = len(head) + (k - 1) * max((len(m) for m in mids), default=0) + max((len(l) for l in lasts), default=0)
+        self.Lmax = max(longest, len(empty))
+
+    def row(self, picks: Sequence[int]) -> List[int]:
+        """The token row k_compose_prompts writes for the entities ``picks`` (indices, in order): the host statement of the device rule."""
+        ids, off, length = self.ids.cpu().tolist(), self.off_host, self.length_host
+        if not picks:
+            return ids[self.empty_off:self.empty_off + self.empty_len]
+        out = ids[self.head_off:self.head_off + self.head_len]
+        for r, e in enumerate(picks):
+            f = 2 * int(e) + (1 if r + 1 == len(picks) else 0)
+            out += ids[off[f]:off[f] + length[f]]
+        return out
+
+    def check(self) -> None:
+        if self.bad:
+            raise ValueError("the hard prompt of entit%s %s does not tokenise as the concatenation of its fragments with this tokenizer: "
+                             "the device-composed prompt (forward_async / TraceCaptionPipeline) is not available; forward() is"
+                             % ("y" if len(self.bad) == 1 else "ies", ", ".join(repr(e) for e in self.bad[:8]) + (" ..." if len(self.bad) > 8 else "")))
+        if not self.empty_ok:
+            raise ValueError("the tokenizer does not encode the empty hard prompt deterministically")
+
+    def to(self, device) -> "PromptFragments":
+        """The three tables on ``device`` (an H2D copy that waits: done at head construction, not on the enqueue path)."""
+        self.ids, self.off, self.length = (t.to(device) for t in (self.ids, self.off, self.length))
+        return self
+
+
 DEFAULTS = {  # VieCap.defaults (entrypoint.py:61-80)
     "language_model": "gpt2", "continuous_prompt_length": 10, "clip_project_length": 10, "temperature": 0.01, "top_k": 3,
     "threshold": 0.2, "disable_all_entities": False, "name_of_entities_text": "vinvl_vgoi_entities", "prompt_ensemble": False,
@@ -233,6 +306,101 @@ class VieCapHead:
         engine.viecap_set_entities(emb)
         # eos ids as greedy_search takes them (search.py:141): the LAST token of "." and of " ."
         self.eos = [self.tokenizer.encode(e)[-1] for e in (".", " .")]
+        self.pad_id = self.tokenizer.pad_token_id if self.tokenizer.pad_token_id is not None else 0
+        # the hard prompt as device-composable fragments (forward_async, the pipeline); checked against the tokenizer here
+        self.fragments = None
+        if a.using_hard_prompt:
+            if not 1 <= int(a.top_k) <= 8:
+                self.fragment_error = "viecap.top_k must be 1..8 for the device-composed hard prompt (%r)" % (a.top_k,)
+            else:
+                self.fragments = PromptFragments(self.tokenizer, self.entities_text, int(a.top_k))
+                if not self.fragments.bad:
+                    self.fragments.to(self.device)
+
+    def check_device_path(self) -> None:
+        """Raises unless this head can run enqueue-only (``enqueue``): greedy search, and a hard prompt that decomposes into fragments."""
+        if not self.args.using_greedy_search:
+            raise ValueError("the device path of the ViECap head is greedy search only (viecap.using_greedy_search=False: beam search)")
+        if self.args.using_hard_prompt:
+            if self.fragments is None:
+                raise ValueError(self.fragment_error)
+            self.fragments.check()
+            if int(self.args.top_k) > len(self.entities_text):
+                raise ValueError("viecap.top_k above the number of entities")
+        Lc, Lmax = self.prompt_shape()
+        if Lc + Lmax > 128 or Lc + Lmax + self.steps - 1 > self.engine.max_steps:
+            raise ValueError("the device path decodes every row at the longest possible prompt: %d soft + %d hard-prompt positions (top_k = %s "
+                             "and the longest entity) + %d steps is above %s; forward() pads to each call's longest prompt instead"
+                             % (Lc, Lmax, self.args.top_k, self.steps - 1,
+                                "128 prompt positions" if Lc + Lmax > 128 else "max_steps = %d" % self.engine.max_steps))
+
+    @property
+    def steps(self) -> int:
+        return 64                                                       # greedy_search's max_len (search.py:108)
+
+    def prompt_shape(self):
+        """(soft prompt rows Lc, or 0 under only_hard_prompt; hard-prompt row width Lmax, or 0 without a hard prompt) of ``stage``."""
+        a = self.args
+        Lc = 0 if (a.using_hard_prompt and a.only_hard_prompt) else int(self.engine.lib.pio_viecap_prompt_length(self.engine.h))
+        return Lc, (self.fragments.Lmax if a.using_hard_prompt else 0)
+
+    def stage(self, image_features: torch.Tensor):
+        """Enqueue-only first half of ``forward`` for ONE caption call: mapping network, entity probabilities, hard prompt composed on the
+        device (viecap.hip) -> (soft prompt [N, Lc, E] or None, token rows [N, Lmax] int32 or None, hard-prompt lengths [N] int32 or None).
+        The features are L2-normalised in place, as in ``forward``.  Nothing here waits for the device."""
+        a, eng = self.args, self.engine
+        x = image_features
+        xd = x.to(device=eng.device, dtype=torch.float32).contiguous()
+        cont = eng.viecap_mapping(xd)
+        if xd.data_ptr() != image_features.data_ptr():
+            image_features.copy_(xd)
+        tokens = lens = None
+        if a.using_hard_prompt:
+            probs = eng.viecap_entity_logits(xd, a.temperature)
+            tokens, lens = eng.viecap_compose_prompts(probs, self.fragments, int(a.top_k), float(a.threshold), self.pad_id)
+        if a.using_hard_prompt and a.only_hard_prompt:
+            cont = None
+        return cont, tokens, lens
+
+    def soft_first(self) -> bool:
+        return bool(self.args.soft_prompt_first) or not self.args.using_hard_prompt
+
+    def enqueue(self, image_features: torch.Tensor) -> torch.Tensor:
+        """``forward`` up to the greedy ids [N, 64] (device), for a greedy head, without a host copy or a sync: ``stage`` + the ragged
+        prompted decode (each row at its call's padded prompt length, which only the device knows).  ``captions(ids.tolist())`` then
+        gives what ``forward`` returns."""
+        self.check_device_path()
+        if not isinstance(image_features, torch.Tensor):
+            image_features = torch.tensor(image_features, dtype=torch.float)
+        cont, tokens, lens = self.stage(image_features)
+        if tokens is None:
+            ids = self.engine.viecap_decode(cont, None, soft_first=True, steps=self.steps)   # no hard prompt: forward's own call
+        else:
+            ids = self.engine.viecap_decode_ragged(cont, tokens, lens, soft_first=self.soft_first(), steps=self.steps)
+        self.last_ids = ids
+        return ids
+
+    def captions(self, rows: List[List[int]]):
+        """Greedy ids -> what ``forward`` returns: each row cut at its first end-of-sentence id and detokenised; a single row comes back
+        as a str (search.py:172-181)."""
+        if len(rows) == 1:
+            # search.py:172-181: a single caption stops at its first full stop and comes back as a str, not a list
+            r = rows[0]
+            out = self.tokenizer.decode(r)
+            for i, t in enumerate(r):
+                if t in self.eos:
+                    out = self.tokenizer.decode(r[:i + 1])
+                    break
+            return out
+        out = []
+        for r in rows:
+            i = len(r) - 1
+            for j, t in enumerate(r):
+                if t in self.eos:
+                    i = j
+                    break
+            out.append(self.tokenizer.decode(r[:i + 1]))
+        return out
 
     def forward(self, image_features: torch.Tensor, compute_scores: bool = False):
         """entrypoint.py:98-153.  image_features [N, clip_hidden_size] is L2-normalised IN PLACE (line 108)."""
@@ -271,24 +439,7 @@ class VieCapHead:
             return out
         ids = eng.viecap_decode(cont, tokens, soft_first=soft_first, steps=64)
         self.last_ids = ids
-        rows = ids.cpu().tolist()
-        if N == 1:
-            # search.py:172-181: a single caption stops at its first full stop and comes back as a str, not a list
-            r = rows[0]
-            out = self.tokenizer.decode(r)
-            for i, t in enumerate(r):
-                if t in self.eos:
-                    out = self.tokenizer.decode(r[:i + 1])
-                    break
-        else:
-            out = []
-            for r in rows:
-                i = len(r) - 1
-                for j, t in enumerate(r):
-                    if t in self.eos:
-                        i = j
-                        break
-                out.append(self.tokenizer.decode(r[:i + 1]))
+        out = self.captions(ids.cpu().tolist())
         if compute_scores:
             return out, self.compute_perplexity(out)
         return out
