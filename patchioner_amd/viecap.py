@@ -114,12 +114,16 @@ def compose_discrete_prompt_text(entities: Sequence[str]) -> str:
 
 
 def top_k_entities(texts: Sequence[str], probs_row: Sequence[float], top_k: int, threshold: float) -> List[str]:
-    """top_k_categories (P/src/viecap/retrieval_categories.py:97-116) for one image: torch.topk order, cut at the first
-    probability below the threshold."""
-    vals, idx = torch.topk(torch.as_tensor(probs_row), k=top_k, dim=-1)
+    """top_k_categories (P/src/viecap/retrieval_categories.py:97-116) for one image, in the order k_compose_prompts fixes: larger first,
+    NaN before any number, equal values by the lower index (torch.topk leaves exact ties unordered).  A stable descending sort gives
+    exactly that.  The cut is at the first probability below the threshold, compared in fp32 as the reference compares its fp32 tensor
+    with the Python float (and as the device does): a probability equal to float32(threshold) is kept, also where that rounds below it."""
+    p = torch.as_tensor(probs_row, dtype=torch.float32).reshape(-1)
+    vals, idx = torch.sort(p, descending=True, stable=True)
+    keep = ~(vals[:top_k] < torch.tensor(threshold, dtype=torch.float32))     # NaN is not below the threshold: kept
     out = []
-    for v, i in zip(vals.tolist(), idx.tolist()):
-        if v < threshold:
+    for k, i in zip(keep.tolist(), idx[:top_k].tolist()):
+        if not k:
             break
         out.append(texts[i])
     return out
