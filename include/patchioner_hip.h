@@ -273,6 +273,22 @@ int pio_lm_advance(pio_handle h, const int32_t* tokens_dev, const int32_t* src_r
 int pio_beam_select(pio_handle h, const float* logp_dev, const float* scores_dev, const float* lens_dev, const int32_t* stopped_dev,
                     int32_t W, float* out_val_dev, int64_t* out_idx_dev, pio_stream stream);
 
+/* Beam search of many images at once, enqueue-only and graph-captured: N images x W beams are the rows of one decode, every selection
+ * and its bookkeeping run on the device, nothing waits for it.  Image n gets, bit for bit, what the three calls above and the host's
+ * fp32 bookkeeping give for it alone (VieCapHead.beam_search): its prompt embeds_dev[n, :P_n] (P_n = plen_dev[n], device memory,
+ * 1 <= P_n <= Pmax; plen_dev NULL: all Pmax) is prefilled once (the W beams share those keys / values), then `steps` selections
+ * (64: the reference's max_len) with eos ids eos0 / eos1.  An image whose W beams have all stopped keeps its state (the reference's break).
+ * Results per image and beam, in the order of the last selection: ids_dev [N, W, steps] int32 (the beam's tokens; read the first lens
+ * of them; -1 past the image's last selection), lens_dev [N, W] int32, scores_dev [N, W] fp32 = accumulated score / length.
+ * Bounds: 1 <= W <= 8 (PIO_ERR_INVALID_ARG), N * W <= min(max_prefixes, 128), 1 <= Pmax <= 128, 1 <= steps <= 64 and
+ * Pmax + steps - 1 <= max_steps (PIO_ERR_CAPACITY).  The graph depends on (N, W, Pmax, steps); works on decoder clones.
+ * pio_viecap_build_prompt_ragged lays the ViECap prompts out for it: prompt_dev [N, Lc + Ltmax, 768], row n = cont[n] and
+ * tokens[n, :lens[n]] in soft_first order, zero past P_n; plen_dev [N] = Lc + lens[n] (pio_viecap_decode_ragged's layout). */
+int pio_viecap_build_prompt_ragged(pio_handle h, const float* cont_dev, const int32_t* tokens_dev, const int32_t* lens_dev, int32_t N,
+                                   int32_t Ltmax, int32_t soft_first, float* prompt_dev, int32_t* plen_dev, pio_stream stream);
+int pio_lm_beam_search(pio_handle h, const float* embeds_dev, const int32_t* plen_dev, int32_t N, int32_t Pmax, int32_t W, int32_t steps,
+                       int32_t eos0, int32_t eos1, int32_t* ids_dev, int32_t* lens_dev, float* scores_dev, pio_stream stream);
+
 /* -- measurement: live HIP-event timing of the launches a call makes, on the stream they are launched on.
  *    While enabled every bracketed launch records a (start, stop) event pair; pio_profile_read waits for the
  *    recorded events of one class and returns the summed device time, the launch count and the ALGORITHMIC

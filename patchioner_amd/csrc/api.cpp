@@ -147,8 +147,11 @@ struct pio_context {
   // ragged: a pio_viecap_decode_ragged graph (P = the upper bound Pmax; the lengths are read from plen_buf)
   struct PKey {
     int N, P, steps, ragged;
+    int eos0 = 0, eos1 = 0;        // batched beam search: its end-of-sentence ids are kernel arguments of the graph
     bool operator<(const PKey& o) const {
-      return N != o.N ? N < o.N : (P != o.P ? P < o.P : (steps != o.steps ? steps < o.steps : ragged < o.ragged));
+      if (N != o.N || P != o.P || steps != o.steps || ragged != o.ragged)
+        return N != o.N ? N < o.N : (P != o.P ? P < o.P : (steps != o.steps ? steps < o.steps : ragged < o.ragged));
+      return eos0 != o.eos0 ? eos0 < o.eos0 : eos1 < o.eos1;
     }
   };
   // prompted-decode graphs, keyed by (rows, prompt positions, steps).  The prompt length follows the hard prompt of every batch,
@@ -162,6 +165,10 @@ struct pio_context {
   float bank_scale = 0.f;   // > 0: the projection runs on split fp16 operands of bank * bank_scale (project.hip) ...
   float* bank_split = nullptr;   // ... [rows][2][dim] fp16 (hi plane, lo plane), the same bytes again as the fp32 bank
   float *beam_k = nullptr, *beam_v = nullptr, *beam_stats = nullptr;   // beam search: KV gather scratch (allocated on first use), row statistics
+  // batched beam search (pio_lm_beam_search): state of min(max_prefixes, 128) rows, allocated with the decoder workspaces (every handle
+  // and clone has its own); the log-probabilities [rows][V] live in `logits`
+  float* bs_f = nullptr;       // stats [R][2], scores [R], lens [R], result scores [R]
+  int32_t* bs_i = nullptr;     // prow, pimg, tok, stopped, prompt lengths, result lengths [R] each, tab [R][max_steps], hist [R][64]
   float *part_acc = nullptr, *part_ml = nullptr, *sims = nullptr;
   int parts = 512;   // two k_project workgroups per CU
   // device-side image transforms (pio_preprocess): growable intermediate image, a ring of table slots
@@ -543,6 +550,9 @@ int alloc_decoder_workspaces(pio_context* c) {
   if ((rc = c->dmalloc(&c->prefix_buf, N * PS, true))) return rc;
   if ((rc = c->dmalloc(&c->logprob_buf, N * S, true))) return rc;
   if ((rc = c->dmalloc(&c->ids_buf, N * S, true))) return rc;
+  const size_t R = N < 128 ? N : 128;
+  if ((rc = c->dmalloc(&c->bs_f, R * 5, true))) return rc;
+  if ((rc = c->dmalloc(&c->bs_i, R * (6 + S + 64), true))) return rc;
   return PIO_OK;
 }
 
@@ -1434,6 +1444,7 @@ hipError_t launch_build_prompt_ragged(const float* cont, const int32_t* tokens, 
                                       int E, int V, int soft_first, float* prompt, int32_t* plen, hipStream_t s) __attribute__((weak));
 hipError_t launch_decode_prompted_ragged(const DecoderArgs& a, const float* prompt, int Pmax, const int32_t* plen, int split, hipStream_t s)
     __attribute__((weak));
+hipError_t launch_lm_beam_search(const DecoderArgs& a, const BeamArgs& b, hipStream_t s) __attribute__((weak));
 }  // namespace pio
 }  // extern "C++"
 
@@ -1598,6 +1609,70 @@ int pio_viecap_decode_ragged(pio_handle c, const float* cont, const int32_t* tok
     HIP_OK(launch_decode_prompted_ragged(a, c->prompt_buf, Pmax, plen, split, s));
   }
   HIP_OK(hipMemcpyAsync(ids, c->ids_buf, (size_t)N * steps * 4, hipMemcpyDeviceToDevice, s));
+  return PIO_OK;
+}
+
+int pio_viecap_build_prompt_ragged(pio_handle c, const float* cont, const int32_t* tokens, const int32_t* lens, int32_t N, int32_t Ltmax,
+                                   int32_t soft_first, float* prompt, int32_t* plen, pio_stream stream) {
+  if (!c || !prompt || !plen || (Ltmax > 0 && (!tokens || !lens))) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_build_prompt_ragged: null argument");
+  if (!cont && Ltmax < 1) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_build_prompt_ragged: neither a soft prompt nor prompt tokens");
+  const pio_context* owner = c->parent ? c->parent : c;
+  if (!c->has_dec || (cont && !owner->has_map))
+    return fail(PIO_ERR_NOT_READY, "pio_viecap_build_prompt_ragged: language model / mapping network not loaded");
+  if (N < 1 || Ltmax < 0) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_build_prompt_ragged: bad shape");
+  if (!launch_build_prompt_ragged) return fail(PIO_ERR_NOT_READY, "pio_viecap_build_prompt_ragged: built without the kernels");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  HIP_OK(launch_build_prompt_ragged(cont, tokens, Ltmax > 0 ? lens : nullptr, c->wte, N, cont ? owner->map_Lc : 0, Ltmax, c->cfg.dec_embd,
+                                    c->cfg.dec_vocab, soft_first, prompt, plen, (hipStream_t)stream));
+  return PIO_OK;
+}
+
+int pio_lm_beam_search(pio_handle c, const float* embeds, const int32_t* plen, int32_t N, int32_t Pmax, int32_t W, int32_t steps, int32_t eos0,
+                       int32_t eos1, int32_t* ids, int32_t* lens, float* scores, pio_stream stream) {
+  if (!c || !embeds || !ids || !lens || !scores) return fail(PIO_ERR_INVALID_ARG, "pio_lm_beam_search: null argument");
+  if (!c->has_dec) return fail(PIO_ERR_NOT_READY, "pio_lm_beam_search: language model not loaded");
+  if (!launch_lm_beam_search) return fail(PIO_ERR_NOT_READY, "pio_lm_beam_search: built without the kernels");
+  if (W < 1 || W > 8) return fail(PIO_ERR_INVALID_ARG, "pio_lm_beam_search: beam width must be 1..8");
+  const int cap = c->cfg.max_prefixes < 128 ? c->cfg.max_prefixes : 128;
+  if (N < 1 || N * W > cap) return fail(PIO_ERR_CAPACITY, "pio_lm_beam_search: N * W above min(max_prefixes, 128) rows");
+  if (Pmax < 1 || Pmax > 128) return fail(PIO_ERR_CAPACITY, "pio_lm_beam_search: prompt positions must be 1..128");
+  if (steps < 1 || steps > 64 || Pmax + steps - 1 > c->cfg.max_steps)
+    return fail(PIO_ERR_CAPACITY, "pio_lm_beam_search: prompt + generated positions above max_steps (or steps outside 1..64)");
+  if (c->cfg.dec_embd != 768 || eos0 < 0 || eos1 < 0 || eos0 >= c->cfg.dec_vocab || eos1 >= c->cfg.dec_vocab)
+    return fail(PIO_ERR_INVALID_ARG, "pio_lm_beam_search: 768-wide language model and eos ids inside the vocabulary required");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = prompted_workspaces(c, true))) return rc;          // the batched prefill workspace (allocated once per handle)
+  const int R = N * W, Rc = cap, S = c->cfg.max_steps;
+  DecoderArgs a = lm_args(c, R);
+  a.steps = steps;
+  a.pre_x = c->pre_x; a.pre_qkv = c->pre_qkv; a.pre_att = c->pre_att; a.pre_hid = c->pre_hid; a.pre_rows = pio_context::kPrefillRows;
+  BeamArgs b;
+  // a captured graph reads the handle's buffers only: the prompts and their lengths are copied in, the results out
+  const size_t E = c->cfg.dec_embd;
+  int32_t* plen_in = c->bs_i + 4 * Rc;
+  HIP_OK(hipMemcpyAsync(c->prompt_buf, embeds, (size_t)N * Pmax * E * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (plen) HIP_OK(hipMemcpyAsync(plen_in, plen, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  b.embeds = c->prompt_buf; b.plen = plen ? plen_in : nullptr; b.N = N; b.Pmax = Pmax; b.W = W; b.steps = steps; b.eos0 = eos0; b.eos1 = eos1;
+  b.npos = c->cfg.dec_positions < S ? c->cfg.dec_positions : S;
+  b.ids = c->ids_buf; b.out_lens = c->bs_i + 5 * Rc; b.out_scores = c->bs_f + 4 * Rc;
+  b.stats = c->bs_f; b.scores = c->bs_f + 2 * Rc; b.lens = c->bs_f + 3 * Rc;
+  b.logp = c->logits;                                          // [R][V]: max_prefixes x round_up(V, 64) floats
+  b.prow = c->bs_i; b.pimg = c->bs_i + Rc; b.tok = c->bs_i + 2 * Rc; b.stopped = c->bs_i + 3 * Rc;
+  b.tab = c->bs_i + 6 * Rc; b.hist = c->bs_i + (size_t)6 * Rc + (size_t)Rc * S;
+  HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
+  if (c->use_graph) {
+    // graphs keyed on (N, Pmax, steps), W, whether plen is given (PKey::ragged = 16 + W (+ 16 without plen): apart from the prompted
+    // decodes' 0 / 1) and the eos ids; the lengths themselves are read from the device
+    if ((rc = launch_prompted_graph(c, pio_context::PKey{N, Pmax, steps, 16 + W + (plen ? 0 : 16), eos0, eos1}, [&](hipStream_t cs) { return launch_lm_beam_search(a, b, cs); }, s)))
+      return rc;
+  } else {
+    HIP_OK(launch_lm_beam_search(a, b, s));
+  }
+  HIP_OK(hipMemcpyAsync(ids, b.ids, (size_t)R * steps * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemcpyAsync(lens, b.out_lens, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemcpyAsync(scores, b.out_scores, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, s));
   return PIO_OK;
 }
 

@@ -420,10 +420,20 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? PIO_DEC_GEMM_WAVES : 1) void k
 // device memory; the loop bodies are the uniform kernel's, so a row attends over its keys exactly as the uniform kernel does for that count.
 // MASK (ragged prefill, decoder.hip: launch_decode_prompted_ragged): 1 = append keys / values only for prefixes with plen[n] <= split,
 // 2 = only for plen[n] > split; the others keep what the other prefill pass wrote.  Everything else is the uniform kernel.
-template <bool RAG = false, int MASK = 0>
+// TAB (batched beam search, launch_lm_beam_search; with RAG): key / value j < pos of row n is read from physical row tab[n][j] (tab: [rows][tstride],
+// clamped to the launch's rows) instead of row n; the new key / value still goes to row n's own slot.  Same loads in the same order: only addresses.
+__device__ __forceinline__ const float* dec_tab_row(const float* cache, const int32_t* __restrict__ tab, int n, int j, int tstride, int max_steps,
+                                                    int E, int heads, int off) {
+  const int rows = (int)gridDim.x / heads;
+  int r = tab[(size_t)n * tstride + j];
+  r = r < 0 ? 0 : (r >= rows ? rows - 1 : r);
+  return cache + ((size_t)r * max_steps + j) * E + off;
+}
+template <bool RAG = false, int MASK = 0, bool TAB = false>
 __global__ __launch_bounds__(256) void k_dec_attention(const float* __restrict__ qkv, float* kcache, float* vcache,
                                                        int E, int heads, int pos0, int max_steps, float* att, int rows_per_n,
-                                                       const int32_t* __restrict__ plen = nullptr, int split = 0) {
+                                                       const int32_t* __restrict__ plen = nullptr, int split = 0,
+                                                       const int32_t* __restrict__ tab = nullptr, int tstride = 0) {
   __shared__ float s_sc[256];
   __shared__ __attribute__((aligned(16))) float s_o[5][256];
   const int n = blockIdx.x / heads, h = blockIdx.x - n * heads;
@@ -450,7 +460,9 @@ __global__ __launch_bounds__(256) void k_dec_attention(const float* __restrict__
 #pragma unroll
   for (int i = 0; i < VPRE; ++i) {
     const int j = jg + NJ * i;
-    vpre[i] = (jg < NJ && j <= pos) ? ((const float4*)(j == pos ? vn : vc + (size_t)j * E))[c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+    vpre[i] = (jg < NJ && j <= pos) ? ((const float4*)(j == pos ? vn : (TAB ? dec_tab_row(vcache, tab, n, j, tstride, max_steps, E, heads, h * hd)
+                                                                          : vc + (size_t)j * E)))[c4]
+                                    : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   {
     const int seg = tid & 7, jl = tid >> 3, per4 = hd >> 5;   // hd/8 channels = per4 float4 (6 for 192)
@@ -458,7 +470,8 @@ __global__ __launch_bounds__(256) void k_dec_attention(const float* __restrict__
       const int j = j0 + jl;
       float s = 0.f;
       if (j <= pos) {
-        const float4* kr = (const float4*)((j == pos ? kn : kc + (size_t)j * E) + seg * (hd >> 3));
+        const float4* kr = (const float4*)((j == pos ? kn : (TAB ? dec_tab_row(kcache, tab, n, j, tstride, max_steps, E, heads, h * hd)
+                                                                 : kc + (size_t)j * E)) + seg * (hd >> 3));
         const float4* qr = (const float4*)(q + seg * (hd >> 3));
         for (int i = 0; i < per4; ++i) {
           const float4 a = kr[i], b = qr[i];
@@ -505,7 +518,8 @@ __global__ __launch_bounds__(256) void k_dec_attention(const float* __restrict__
     }
     for (int j = jg + NJ * VPRE; j <= pos; j += NJ) {
       const float p = s_sc[j];
-      const float4 v = ((const float4*)(j == pos ? vn : vc + (size_t)j * E))[c4];
+      const float4 v = ((const float4*)(j == pos ? vn : (TAB ? dec_tab_row(vcache, tab, n, j, tstride, max_steps, E, heads, h * hd)
+                                                            : vc + (size_t)j * E)))[c4];
       o.x += p * v.x; o.y += p * v.y; o.z += p * v.z; o.w += p * v.w;
     }
     *(float4*)&s_o[jg][4 * c4] = o;
@@ -2010,9 +2024,9 @@ hipError_t launch_lmhead(const float* W, const float* X, int N, int V, int E, co
 }
 
 // One new position `pos` of every prefix through the transformer layers (x in place; keys / values appended at `pos`).
-// RAG: prefix n's position is plen[n] + pos.
+// RAG: prefix n's position is plen[n] + pos.  tab (RAG only; batched beam search): the history of row n is read through tab [N][a.max_steps].
 template <bool RAG = false>
-static hipError_t dec_layers_step(const DecoderArgs& a, int pos, hipStream_t s, const int32_t* plen = nullptr) {
+static hipError_t dec_layers_step(const DecoderArgs& a, int pos, hipStream_t s, const int32_t* plen = nullptr, const int32_t* tab = nullptr) {
   const int N = a.N, E = a.E;
   for (int l = 0; l < a.layers; ++l) {
     const DecLayerW& w = a.layer[l];
@@ -2020,7 +2034,11 @@ static hipError_t dec_layers_step(const DecoderArgs& a, int pos, hipStream_t s, 
     float* vc = a.vcache + (size_t)l * N * a.max_steps * E;
     if constexpr (RAG) {             // every row on the kernels of a one-row decode, whatever the rows of the launch (dec_gemm_cls)
       PIO_TRY((dec_gemm_cls<DE_STORE, 1>(DEC_CLS_A, w.attn_w, a.x, N, 3 * E, E, w.attn_d, a.qkv, w.attn_c, a.eps, nullptr, nullptr, s)));
-      hipLaunchKernelGGL(k_dec_attention<true>, dim3(N * a.heads), dim3(256), 0, s, a.qkv, kc, vc, E, a.heads, pos, a.max_steps, a.att, 1, plen, 0);
+      if (tab != nullptr)
+        hipLaunchKernelGGL((k_dec_attention<true, 0, true>), dim3(N * a.heads), dim3(256), 0, s, a.qkv, kc, vc, E, a.heads, pos, a.max_steps, a.att, 1,
+                           plen, 0, tab, a.max_steps);
+      else
+        hipLaunchKernelGGL(k_dec_attention<true>, dim3(N * a.heads), dim3(256), 0, s, a.qkv, kc, vc, E, a.heads, pos, a.max_steps, a.att, 1, plen, 0);
       PIO_TRY((dec_gemm_cls<DE_RESID, 0>(DEC_CLS_A, w.proj_w, a.att, N, E, E, w.proj_b, a.x, nullptr, 0.f, nullptr, nullptr, s)));
       PIO_TRY((dec_gemm_cls<DE_GELU, 1>(DEC_CLS_A, w.fc_w, a.x, N, 4 * E, E, w.fc_d, a.hid, w.fc_c, a.eps, nullptr, nullptr, s)));
       PIO_TRY((dec_gemm_cls<DE_RESID, 0>(DEC_CLS_A, w.fc2_w, a.hid, N, E, 4 * E, w.fc2_b, a.x, nullptr, 0.f, a.splitk_ws, a.splitk_cnt, s)));
@@ -2260,21 +2278,25 @@ __global__ __launch_bounds__(256) void k_dec_last_rows_ragged(const float* __res
   const size_t r = (size_t)n * Pmax + plen[n] - 1;
   for (int d = threadIdx.x; d < E; d += 256) x[(size_t)n * E + d] = xp[r * E + d];
 }
-// dec_prefill_layers on one GEMM family (dec_gemm_cls), keys / values kept for the prefixes of that family only
+// dec_prefill_layers on one GEMM family (dec_gemm_cls), keys / values kept for the prefixes of that family only.
+// rstride (batched beam search): prefix n's keys / values go to cache row n * rstride (the first beam of image n); the kernels see a row of
+// rstride * max_steps positions, of which the first max_steps are that cache row.
 template <int MASK>
-static hipError_t dec_prefill_layers_masked(const DecoderArgs& a, int n0, int gN, int P, const int32_t* plen, int split, hipStream_t s) {
+static hipError_t dec_prefill_layers_masked(const DecoderArgs& a, int n0, int gN, int P, const int32_t* plen, int split, hipStream_t s,
+                                            int rstride = 1) {
   const int E = a.E, R = gN * P, cls = MASK == 1 ? DEC_CLS_A : DEC_CLS_B;
+  const int ms = a.max_steps * rstride;
   for (int l = 0; l < a.layers; ++l) {
     const DecLayerW& w = a.layer[l];
-    float* kc = a.kcache + ((size_t)l * a.N + n0) * a.max_steps * E;
-    float* vc = a.vcache + ((size_t)l * a.N + n0) * a.max_steps * E;
+    float* kc = a.kcache + ((size_t)l * a.N + (size_t)n0 * rstride) * a.max_steps * E;
+    float* vc = a.vcache + ((size_t)l * a.N + (size_t)n0 * rstride) * a.max_steps * E;
     for (int r0 = 0; r0 < R; r0 += 128) {
       const int rows = R - r0 < 128 ? R - r0 : 128;
       PIO_TRY((dec_gemm_cls<DE_STORE, 1>(cls, w.attn_w, a.pre_x + (size_t)r0 * E, rows, 3 * E, E, w.attn_d, a.pre_qkv + (size_t)r0 * 3 * E, w.attn_c,
                                          a.eps, nullptr, nullptr, s)));
     }
-    hipLaunchKernelGGL(k_kv_append_masked<MASK>, dim3(gN, P), dim3(192), 0, s, a.pre_qkv, kc, vc, P, a.max_steps, E, plen, split);
-    hipLaunchKernelGGL((k_dec_attention<false, MASK>), dim3(gN * a.heads, P), dim3(256), 0, s, a.pre_qkv, kc, vc, E, a.heads, 0, a.max_steps, a.pre_att,
+    hipLaunchKernelGGL(k_kv_append_masked<MASK>, dim3(gN, P), dim3(192), 0, s, a.pre_qkv, kc, vc, P, ms, E, plen, split);
+    hipLaunchKernelGGL((k_dec_attention<false, MASK>), dim3(gN * a.heads, P), dim3(256), 0, s, a.pre_qkv, kc, vc, E, a.heads, 0, ms, a.pre_att,
                        P, plen, split);
     for (int r0 = 0; r0 < R; r0 += 128) {
       const int rows = R - r0 < 128 ? R - r0 : 128;
@@ -2500,6 +2522,277 @@ hipError_t launch_beam_select(const float* logp, const float* scores, const floa
                               float* out_val, int64_t* out_idx, hipStream_t s) {
   if (W < 1 || W > 8 || V < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_beam_select, dim3(1), dim3(1024), 0, s, logp, scores, lens, stopped, W, V, out_val, out_idx);
+  return hipGetLastError();
+}
+
+
+// ---- batched beam search (launch_lm_beam_search): N images x W beams as the rows of one decode, the bookkeeping on the device.
+// Bits: image n gets what VieCapHead.beam_search gives for it alone (pio_lm_prefill / pio_lm_advance / pio_beam_select + the host's fp32
+// bookkeeping), because every number goes through the same operations in the same order:
+//   prefill  -- the per-image path runs the prompt position by position on W identical rows, i.e. on k_dec_gemm (family A, <= 16 rows).
+//               Here the prompts of all images go through the batched prefill on family A (dec_gemm_cls: a row's sums do not depend on
+//               the launch) and the attention of a position keeps its reduction order (grid.y form: same loads per position);
+//               image n's keys / values land in cache row n W, which its W beams share through the table.
+//   steps    -- family A GEMMs on N W rows (dec_layers_step<true>) at row position P_n + i - 1, attention at that row's key count;
+//               the per-image path re-gathers the KV cache of its beams, here k_dec_attention<true, 0, true> reads position j of row r
+//               from cache row tab[r][j].  A row only ever writes its own slot at its current position, so no history is overwritten.
+//   head     -- k_row_stats, k_lm_logits_rows (k_lm_logits_full's sums, batched) and k_log_softmax_rows, one block per row.
+//   select   -- k_beam_step: per image the W largest candidates of k_beam_select's formula (a total order: value descending, flat index
+//               ascending, NaN never enters), then the host's bookkeeping in fp32, in its order; an image whose W beams have all
+//               stopped is frozen (the reference's break): nothing of its state changes any more.
+
+// out[n][v] = k_lm_logits_full's value for every row n < N and column v < V, reading each weight column once per launch: a wave keeps
+// BL_C columns of W in registers (lane l: d = l + 64 j) and walks all N rows.  Per (row, column): lane l's fmaf chain over j ascending,
+// wave_sum's tree, then rstd (acc - mu c) + d as two fmas -- the instructions hipcc emits for k_lm_logits_full's expression (fp-contract).
+static constexpr int BL_C = 8;            // columns per wave
+__global__ __launch_bounds__(256) void k_lm_logits_rows(const float* __restrict__ W, const float* __restrict__ X, int N, int V,
+                                                        const float* __restrict__ dvec, const float* __restrict__ cvec,
+                                                        const float* __restrict__ stats, float* __restrict__ out) {
+  constexpr int E = 768, J = E / 64;
+  const int lane = threadIdx.x & 63;
+  const int v0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * BL_C;
+  if (v0 >= V) return;                                   // wave-uniform
+  float w[BL_C][J];
+  float cv[BL_C], dv[BL_C];
+#pragma unroll
+  for (int c = 0; c < BL_C; ++c) {
+    const int v = v0 + c < V ? v0 + c : V - 1;
+#pragma unroll
+    for (int j = 0; j < J; ++j) w[c][j] = W[(size_t)v * E + lane + 64 * j];
+    cv[c] = cvec[v];
+    dv[c] = dvec[v];
+  }
+  float xa[J];
+#pragma unroll
+  for (int j = 0; j < J; ++j) xa[j] = X[lane + 64 * j];
+  for (int n = 0; n < N; ++n) {
+    float xb[J];
+    const int nn = n + 1 < N ? n + 1 : n;               // next row's activations in flight under this row's work
+#pragma unroll
+    for (int j = 0; j < J; ++j) xb[j] = X[(size_t)nn * E + lane + 64 * j];
+    const float mu = stats[2 * n], rstd = stats[2 * n + 1];
+    float res = 0.f;
+#pragma unroll
+    for (int c = 0; c < BL_C; ++c) {
+      float acc = 0.f;
+#pragma unroll
+      for (int j = 0; j < J; ++j) acc = fmaf(xa[j], w[c][j], acc);
+      acc = wave_sum(acc);
+      const float o = __builtin_fmaf(rstd, __builtin_fmaf(-mu, cv[c], acc), dv[c]);
+      res = lane == c ? o : res;
+    }
+    if (lane < BL_C && v0 + lane < V) out[(size_t)n * V + v0 + lane] = res;
+#pragma unroll
+    for (int j = 0; j < J; ++j) xa[j] = xb[j];
+  }
+}
+
+// k_beam_select's candidates of one image, from the rows lp[b][.] (b < rows): first (scores == null) lp[0][v]; otherwise stopped[b] ?
+// (v == 0 ? scores[b] / lens[b] : -inf) : (scores[b] + lp[b][v]) / (lens[b] + 1).  The W largest (value descending, flat index b V + v
+// ascending on ties, NaN skipped) -> s_val[W], s_idx[W] (shared).  A thread walks its candidates in ascending flat order (b outer, v = tid
+// + 1024 k inner), so equal values keep the lower index first in its list, as in k_beam_select.  Block of 1024 threads.
+__device__ void beam_topw(const float* __restrict__ lp, const float* scores, const float* lens, const int32_t* stopped, int W, int V,
+                          float* s_val, int* s_idx) {
+  __shared__ float s_v[16];
+  __shared__ int s_i[16];
+  __shared__ int s_win;
+  const int tid = threadIdx.x;
+  float bv[8];
+  int bi[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { bv[k] = -INFINITY; bi[k] = -1; }
+  const int rows = scores ? W : 1;
+  for (int b = 0; b < rows; ++b) {
+    const bool st = scores ? stopped[b] != 0 : false;
+    const float sc = scores ? scores[b] : 0.f, ln = scores ? lens[b] : 1.f;
+    const float* row = lp + (size_t)b * V;
+    for (int v = tid; v < V; v += 1024) {
+      float val;
+      if (!scores) val = row[v];
+      else if (st) val = v == 0 ? sc / ln : -INFINITY;
+      else val = (sc + row[v]) / (ln + 1.0f);
+      if (!(val > bv[7]) && bi[7] >= 0) continue;
+      if (!(val == val)) continue;
+      const int c = b * V + v;
+      int k = 7;
+      while (k > 0 && (bi[k - 1] < 0 || val > bv[k - 1])) { bv[k] = bv[k - 1]; bi[k] = bi[k - 1]; --k; }
+      bv[k] = val; bi[k] = c;
+    }
+  }
+  int head = 0;
+  for (int round = 0; round < W; ++round) {
+    float v = head < 8 ? bv[head] : -INFINITY;
+    int i = head < 8 ? bi[head] : -1;
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(v, o);
+      const int oi = __shfl_xor(i, o);
+      if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) { v = ov; i = oi; }
+    }
+    if ((tid & 63) == 0) { s_v[tid >> 6] = v; s_i[tid >> 6] = i; }
+    __syncthreads();
+    if (tid == 0) {
+      float fv = s_v[0]; int fi = s_i[0];
+      for (int w = 1; w < 16; ++w)
+        if (s_i[w] >= 0 && (fi < 0 || s_v[w] > fv || (s_v[w] == fv && s_i[w] < fi))) { fv = s_v[w]; fi = s_i[w]; }
+      s_val[round] = fv;
+      s_idx[round] = fi;
+      s_win = fi >= 0 ? (fi % V) % 1024 : -1;          // the thread that owns candidate fi (v = tid + 1024 k)
+    }
+    __syncthreads();
+    if (tid == s_win) ++head;
+    __syncthreads();
+  }
+}
+
+// Per row r = n W + b: prompt length, table (positions < P_n: the shared prompt row n W; later positions: the row's own slot), no tokens yet.
+__global__ __launch_bounds__(256) void k_beam_init(const int32_t* __restrict__ plen, int Pmax, int W, int tstride, int steps, int32_t* prow,
+                                                   int32_t* pimg, int32_t* tab, int32_t* hist) {
+  const int r = blockIdx.x, n = r / W;
+  int P = plen ? plen[n] : Pmax;
+  P = P < 1 ? 1 : (P > Pmax ? Pmax : P);
+  if (threadIdx.x == 0) { prow[r] = P; if (r == n * W) pimg[n] = P; }
+  for (int j = threadIdx.x; j < tstride; j += 256) tab[(size_t)r * tstride + j] = j < P ? n * W : r;
+  for (int k = threadIdx.x; k < steps; k += 256) hist[(size_t)r * steps + k] = -1;
+}
+
+// Selection `step` of image n (blockIdx.x) and the host's bookkeeping after it (search.py:247-270 as VieCapHead.beam_search restates it):
+//   lens[~stopped] += 1;  src = flat // V;  tok = flat % V;  lens = lens[src];  scores = avg * lens;  stopped = stopped[src] | tok in eos;
+// the token histories and the key / value tables follow src.  Then x of the image's rows = wte[tok] + wpe[P_n + step] (the next step's input).
+// step 0: the W largest of row n of lp (the prefill's last position), scores = values, lens = 1.  An image whose beams have all stopped
+// before this step is frozen: only x is rewritten (its rows still run, their results unused).  Everything in place: one workgroup owns
+// the image's state and reads all of it before writing any.
+__global__ __launch_bounds__(1024) void k_beam_step(const float* __restrict__ lp, int W, int V, int step, int eos0, int eos1,
+                                                    const int32_t* __restrict__ prow, float* scores, float* lens, int32_t* stopped,
+                                                    int32_t* tok, int32_t* hist, int steps, int32_t* tab, int tstride,
+                                                    const float* __restrict__ wte, const float* __restrict__ wpe, int npos, int E, float* x) {
+  __shared__ float s_val[8];
+  __shared__ int s_idx[8];
+  __shared__ int s_frozen;
+  __shared__ float s_lens[8];
+  __shared__ int s_stop[8], s_tok[8], s_src[8];
+  __shared__ int s_hist[8][64];
+  __shared__ int s_tab[8][256];
+  const int n = blockIdx.x, r0 = n * W, tid = threadIdx.x;
+  const int P = prow[r0];
+  if (step == 0) {
+    beam_topw(lp + (size_t)n * V, nullptr, nullptr, nullptr, W, V, s_val, s_idx);
+    if (tid < W) {
+      const int t = s_idx[tid];
+      scores[r0 + tid] = s_val[tid];
+      lens[r0 + tid] = 1.0f;
+      stopped[r0 + tid] = (t == eos0) | (t == eos1);
+      tok[r0 + tid] = t;
+      hist[(size_t)(r0 + tid) * steps] = t;
+      s_tok[tid] = t;
+    }
+  } else {
+    if (tid == 0) {
+      int all = 1;
+      for (int b = 0; b < W; ++b) all &= stopped[r0 + b] != 0;
+      s_frozen = all;
+    }
+    __syncthreads();
+    if (s_frozen) {
+      if (tid < W) s_tok[tid] = tok[r0 + tid];
+    } else {
+      beam_topw(lp + (size_t)r0 * V, scores + r0, lens + r0, stopped + r0, W, V, s_val, s_idx);
+      const int pos = P + step - 1;                    // the position this step's layers just wrote
+      if (tid < W) {
+        const int st = stopped[r0 + tid];
+        s_stop[tid] = st;
+        s_lens[tid] = st ? lens[r0 + tid] : lens[r0 + tid] + 1.0f;      // seq_lengths[~is_stopped] += 1
+      }
+      for (int e = tid; e < W * 64; e += 1024) {
+        const int b = e / 64, k = e - b * 64;
+        s_hist[b][k] = k < step ? hist[(size_t)(r0 + b) * steps + k] : -1;
+      }
+      for (int e = tid; e < W * 256; e += 1024) {
+        const int b = e / 256, j = e - b * 256;
+        if (j <= pos) s_tab[b][j] = tab[(size_t)(r0 + b) * tstride + j];
+      }
+      __syncthreads();
+      if (tid < W) {
+        const int flat = s_idx[tid];
+        int src = flat / V;
+        src = src < 0 ? 0 : (src >= W ? W - 1 : src);
+        const int t = flat - (flat / V) * V;
+        const float nl = s_lens[src];
+        lens[r0 + tid] = nl;
+        scores[r0 + tid] = __fmul_rn(s_val[tid], nl);
+        stopped[r0 + tid] = s_stop[src] | (t == eos0) | (t == eos1);
+        tok[r0 + tid] = t;
+        s_tok[tid] = t;
+        s_src[tid] = src;
+      }
+      __syncthreads();
+      for (int e = tid; e < W * 64; e += 1024) {
+        const int b = e / 64, k = e - b * 64, src = s_src[b];
+        if (k < step) hist[(size_t)(r0 + b) * steps + k] = s_hist[src][k];
+        else if (k == step) hist[(size_t)(r0 + b) * steps + k] = s_tok[b];
+      }
+      for (int e = tid; e < W * 256; e += 1024) {
+        const int b = e / 256, j = e - b * 256, src = s_src[b];
+        if (j <= pos) tab[(size_t)(r0 + b) * tstride + j] = s_tab[src][j];
+      }
+    }
+  }
+  __syncthreads();
+  const int xpos = P + step < npos ? P + step : npos - 1;     // the last step's input is never used: kept inside wpe
+  for (int e = tid; e < W * E; e += 1024) {
+    const int b = e / E, d = e - b * E;
+    int t = s_tok[b];
+    t = t < 0 ? 0 : (t >= V ? V - 1 : t);
+    x[(size_t)(r0 + b) * E + d] = wte[(size_t)t * E + d] + wpe[(size_t)xpos * E + d];
+  }
+}
+
+// results per row: token ids [steps], length, scores / lens (correctly rounded, as numpy divides)
+__global__ __launch_bounds__(64) void k_beam_finish(const int32_t* __restrict__ hist, const float* __restrict__ scores,
+                                                    const float* __restrict__ lens, int steps, int32_t* ids, int32_t* out_lens, float* out_scores) {
+  const int r = blockIdx.x;
+  for (int k = threadIdx.x; k < steps; k += 64) ids[(size_t)r * steps + k] = hist[(size_t)r * steps + k];
+  if (threadIdx.x == 0) {
+    out_lens[r] = (int32_t)lens[r];
+    out_scores[r] = __fdiv_rn(scores[r], lens[r]);
+  }
+}
+
+// logp[rows][V] = log softmax of the LM head on x's first `rows` rows
+static hipError_t beam_head(const DecoderArgs& a, int rows, float* stats, float* logp, hipStream_t s) {
+  hipLaunchKernelGGL(k_row_stats, dim3(rows), dim3(256), 0, s, a.x, a.E, a.eps, stats);
+  hipLaunchKernelGGL(k_lm_logits_rows, dim3(ceil_div(a.vocab, 4 * BL_C)), dim3(256), 0, s, a.head_w, a.x, rows, a.vocab, a.head_d, a.head_c,
+                     stats, logp);
+  hipLaunchKernelGGL(k_log_softmax_rows, dim3(rows), dim3(1024), 0, s, logp, a.vocab);
+  return hipGetLastError();
+}
+
+hipError_t launch_lm_beam_search(const DecoderArgs& a, const BeamArgs& b, hipStream_t s) {
+  const int N = b.N, W = b.W, R = N * W, E = a.E, V = a.vocab;
+  if (N < 1 || W < 1 || W > 8 || R > 128 || a.N != R || b.Pmax < 1 || b.Pmax > 128 || b.steps < 1 || b.steps > 64 ||
+      b.Pmax + b.steps - 1 > a.max_steps || a.max_steps > 256 || E != 768 || a.pre_x == nullptr || b.Pmax > a.pre_rows ||
+      (E / a.heads) % 32 != 0)
+    return hipErrorInvalidValue;
+  const int tstride = a.max_steps;
+  hipLaunchKernelGGL(k_beam_init, dim3(R), dim3(256), 0, s, b.plen, b.Pmax, W, tstride, b.steps, b.prow, b.pimg, b.tab, b.hist);
+  // the prompts, once per image, on family A; image n's keys / values into cache row n W; x[n] = output of position P_n - 1
+  const int split = 1 << 30, Pmax = b.Pmax;
+  const int gmax = a.pre_rows / Pmax;
+  for (int n0 = 0; n0 < N; n0 += gmax) {
+    const int gN = N - n0 < gmax ? N - n0 : gmax;
+    hipLaunchKernelGGL(k_dec_prompt_x_all, dim3(gN, Pmax), dim3(256), 0, s, b.embeds + (size_t)n0 * Pmax * E, a.wpe, Pmax, E, a.pre_x);
+    PIO_TRY(dec_prefill_layers_masked<1>(a, n0, gN, Pmax, b.pimg + n0, split, s, W));
+    hipLaunchKernelGGL(k_dec_last_rows_ragged<1>, dim3(gN), dim3(256), 0, s, a.pre_x, Pmax, b.pimg + n0, split, E, a.x + (size_t)n0 * E);
+  }
+  PIO_TRY(beam_head(a, N, b.stats, b.logp, s));
+  hipLaunchKernelGGL(k_beam_step, dim3(N), dim3(1024), 0, s, b.logp, W, V, 0, b.eos0, b.eos1, b.prow, b.scores, b.lens, b.stopped, b.tok,
+                     b.hist, b.steps, b.tab, tstride, a.wte, a.wpe, b.npos, E, a.x);
+  for (int i = 1; i < b.steps; ++i) {
+    PIO_TRY(dec_layers_step<true>(a, i - 1, s, b.prow, b.tab));     // row r at position P_n + i - 1
+    PIO_TRY(beam_head(a, R, b.stats, b.logp, s));
+    hipLaunchKernelGGL(k_beam_step, dim3(N), dim3(1024), 0, s, b.logp, W, V, i, b.eos0, b.eos1, b.prow, b.scores, b.lens, b.stopped, b.tok,
+                       b.hist, b.steps, b.tab, tstride, a.wte, a.wpe, b.npos, E, a.x);
+  }
+  hipLaunchKernelGGL(k_beam_finish, dim3(R), dim3(64), 0, s, b.hist, b.scores, b.lens, b.steps, b.ids, b.out_lens, b.out_scores);
   return hipGetLastError();
 }
 

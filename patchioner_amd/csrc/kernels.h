@@ -243,6 +243,21 @@ hipError_t launch_lm_advance(const DecoderArgs& a, const int32_t* tokens, const 
                              float* vscratch, float* stats, float* logp, hipStream_t s);
 hipError_t launch_beam_select(const float* logp, const float* scores, const float* lens, const int32_t* stopped, int W, int V,
                               float* out_val, int64_t* out_idx, hipStream_t s);
+// batched beam search: N images x W beams = a.N rows (<= 128, W <= 8), prompts embeds [N][Pmax][E] with plen [N] on the device (null: all
+// Pmax), steps <= 64 selections; the batched prefill workspace is required (a.pre_x).  The state buffers are the handle's (beam_state).
+// Per image and beam, in the order of the last selection: ids [N][W][steps] (-1 past the last selection), lens [N][W], scores / lens [N][W].
+struct BeamArgs {
+  const float* embeds;
+  const int32_t* plen;
+  int N, Pmax, W, steps, eos0, eos1;
+  int npos;                   // rows of wpe
+  int32_t *ids, *out_lens;
+  float* out_scores;
+  // state: stats [R][2], logp [R][V], prow / pimg / tok / stopped [R], scores / lens [R], tab [R][max_steps], hist [R][steps]
+  float *stats, *logp, *scores, *lens;
+  int32_t *prow, *pimg, *tok, *stopped, *tab, *hist;
+};
+hipError_t launch_lm_beam_search(const DecoderArgs& a, const BeamArgs& b, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // ViECap head (viecap.hip): mapping network, entity logits, prompt assembly -- all fp32

@@ -503,6 +503,52 @@ class Engine:
             check(self.lib.pio_beam_select(self.h, ptr(logp), ptr(sc), ptr(ln), ptr(st), W, ptr(val), ptr(idx), _stream()))
         return val.cpu(), idx.cpu()
 
+    # ---- batched beam search: N images x W beams as the rows of one decode, the bookkeeping on the device (pio_lm_beam_search)
+    def lm_beam_search(self, embeds: torch.Tensor, plen: Optional[torch.Tensor], beam_width: int, eos: Sequence[int], steps: int = 64):
+        """embeds [N, Pmax, E] device (image n's prompt: its first plen[n] positions), plen [N] int32 device or None (all Pmax) ->
+        (ids [N, W, steps] int32, lens [N, W] int32, scores [N, W] fp32) on the device, per image and beam in the order of the last
+        selection; image n's are VieCapHead.beam_search's for it alone.  Enqueue-only; chunks of min(max_prefixes, 128) // W images."""
+        embeds = self._dev(embeds).contiguous()
+        W = int(beam_width)
+        N, Pmax = int(embeds.shape[0]), int(embeds.shape[1])
+        ids = torch.empty(N, W, steps, device=self.device, dtype=torch.int32)
+        lens = torch.empty(N, W, device=self.device, dtype=torch.int32)
+        scores = torch.empty(N, W, device=self.device, dtype=torch.float32)
+        if plen is not None:
+            plen = self._dev(plen, torch.int32).contiguous()
+        chunk = max(1, min(self.max_prefixes, 128) // W)
+        for s in range(0, N, chunk):
+            e = min(N, s + chunk)
+            check(self.lib.pio_lm_beam_search(self.h, ptr(embeds[s:e]), ptr(plen[s:e]) if plen is not None else None, e - s, Pmax, W,
+                                              int(steps), int(eos[0]), int(eos[1]), ptr(ids[s:e]), ptr(lens[s:e]), ptr(scores[s:e]),
+                                              _stream()))
+        return ids, lens, scores
+
+    def viecap_build_prompt_ragged(self, cont: Optional[torch.Tensor], tokens: Optional[torch.Tensor], lens: Optional[torch.Tensor],
+                                   soft_first: bool = True):
+        """The prompts of viecap_decode_ragged (pio_viecap_build_prompt_ragged): -> (prompt [N, Lc + Ltmax, E], plen [N] int32), device."""
+        if cont is None and tokens is None:
+            raise ValueError("viecap_build_prompt_ragged: neither a soft prompt nor prompt tokens")
+        if (tokens is None) != (lens is None):
+            raise ValueError("viecap_build_prompt_ragged: tokens and lens go together")
+        N = int(cont.shape[0] if cont is not None else tokens.shape[0])
+        Lt = int(tokens.shape[1]) if tokens is not None else 0
+        Lc = int(cont.shape[1]) if cont is not None else 0
+        prompt = torch.empty(N, Lc + Lt, self.cfg.dec_embd, device=self.device, dtype=torch.float32)
+        plen = torch.empty(N, device=self.device, dtype=torch.int32)
+        check(self.lib.pio_viecap_build_prompt_ragged(self.h, ptr(cont.contiguous()) if cont is not None else None,
+                                                      ptr(tokens.contiguous()) if tokens is not None else None,
+                                                      ptr(lens.contiguous()) if lens is not None else None, N, Lt,
+                                                      1 if soft_first else 0, ptr(prompt), ptr(plen), _stream()))
+        return prompt, plen
+
+    def viecap_beam_ragged(self, cont: Optional[torch.Tensor], tokens: Optional[torch.Tensor], lens: Optional[torch.Tensor],
+                           beam_width: int, eos: Sequence[int], soft_first: bool = True, steps: int = 64):
+        """Beam search of every row of stage()'s (cont, tokens, lens), each at its own prompt length: lm_beam_search on the prompts of
+        viecap_build_prompt_ragged."""
+        prompt, plen = self.viecap_build_prompt_ragged(cont, tokens, lens, soft_first=soft_first)
+        return self.lm_beam_search(prompt, plen, beam_width, eos, steps=steps)
+
     # ------------------------------------------------------------------ a11/a12 decoder
     def decode_greedy(self, prefix: torch.Tensor, steps: int = 30, want_logprob: bool = False):
         prefix = self._dev(prefix)
@@ -519,12 +565,13 @@ class Engine:
 
 
 class DecoderClone:
-    """Handle from pio_clone_decoder: borrows the parent's decoder weights, owns its workspaces.  decode_greedy and viecap_decode_ragged
-    (the soft prompt and the token rows come from the parent: the mapping network and the entity table stay on it)."""
+    """Handle from pio_clone_decoder: borrows the parent's decoder weights, owns its workspaces.  decode_greedy, viecap_decode_ragged and
+    the batched beam search (the soft prompt and the token rows come from the parent: the mapping network and the entity table stay on it)."""
 
     def __init__(self, parent: Engine):
         self.lib, self.parent, self.device = parent.lib, parent, parent.device
         self.max_prefixes, self.max_steps, self.prefix_size = parent.max_prefixes, parent.max_steps, parent.prefix_size
+        self.cfg = parent.cfg
         h = ctypes.c_void_p()
         check(self.lib.pio_clone_decoder(parent.h, ctypes.byref(h)))
         self.h = h
@@ -543,3 +590,6 @@ class DecoderClone:
     _dev = Engine._dev
     decode_greedy = Engine.decode_greedy
     viecap_decode_ragged = Engine.viecap_decode_ragged
+    lm_beam_search = Engine.lm_beam_search
+    viecap_build_prompt_ragged = Engine.viecap_build_prompt_ragged
+    viecap_beam_ragged = Engine.viecap_beam_ragged

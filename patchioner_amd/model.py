@@ -670,10 +670,15 @@ class Patchioner(nn.Module):
         if self.viecap is not None:
             if return_n_best_sims:
                 raise Exception("return_n_best_sims is not supported with viecap")
-            if self._defer and self.viecap.args.using_greedy_search:
-                # forward_async: mapping, entity probabilities, hard prompt and the ragged decode are enqueued; ids -> text in result()
+            if self._defer:
+                # forward_async: mapping, entity probabilities, hard prompt and the ragged decode (greedy) or the batched beam search
+                # are enqueued; ids -> text in result()
                 if compute_scores:
                     raise NotImplementedError("forward_async does not defer score lists; call forward() for compute_scores")
+                if not self.viecap.args.using_greedy_search:
+                    res = self.viecap.enqueue(dino_tokens)
+                    self.last_ids = None              # as forward(): the beams of an image have their own lengths
+                    return _PendingVieCapBeams(res, self.viecap)
                 ids = self.viecap.enqueue(dino_tokens)
                 self.last_ids = ids
                 return _PendingVieCapCaptions(ids, self.viecap)
@@ -772,6 +777,24 @@ class _PendingVieCapCaptions(_PendingCaptions):
 
     def resolve(self):
         return self.head.captions(self.ids_host.tolist())
+
+
+class _PendingVieCapBeams(_PendingCaptions):
+    """A beam head's (ids, lens, scores) still on the device; resolved as VieCapHead.forward returns them (a list, one text per image)."""
+
+    def __init__(self, res, head):
+        super().__init__(res[0], None, None)
+        self.lens_dev, self.scores_dev, self.head = res[1], res[2], head
+
+    def start_copy(self):
+        super().start_copy()
+        self.lens_host = torch.empty(self.lens_dev.shape, dtype=self.lens_dev.dtype).pin_memory()
+        self.lens_host.copy_(self.lens_dev, non_blocking=True)
+        self.scores_host = torch.empty(self.scores_dev.shape, dtype=self.scores_dev.dtype).pin_memory()
+        self.scores_host.copy_(self.scores_dev, non_blocking=True)
+
+    def resolve(self):
+        return self.head.beam_captions(self.ids_host.tolist(), self.lens_host.tolist(), self.scores_host.tolist())
 
 
 class PendingForward:

@@ -60,7 +60,7 @@ def _rows_of(imgs, regions) -> int:
 
 
 class _Group:
-    def __init__(self, cap: int, dim: int, steps: int, device, viecap_shape=None):
+    def __init__(self, cap: int, dim: int, steps: int, device, viecap_shape=None, beam_width: int = 0):
         # viecap_shape (Lc, Lmax, E): a ViECap head's soft prompts [cap, Lc, E], hard-prompt token rows [cap, Lmax] and their lengths
         self.prefix = torch.empty(cap, dim if viecap_shape is None else 1, device=device, dtype=torch.float32)
         self.cont = self.tokens = self.lens = None
@@ -71,7 +71,10 @@ class _Group:
             if Lmax:
                 self.tokens = torch.empty(cap, Lmax, device=device, dtype=torch.int32)
                 self.lens = torch.empty(cap, device=device, dtype=torch.int32)
-        self.ids_host = torch.empty(cap, steps, dtype=torch.int32).pin_memory()
+        self.ids_host = torch.empty((cap, beam_width, steps) if beam_width else (cap, steps), dtype=torch.int32).pin_memory()
+        if beam_width:                    # a beam-search group: lengths and scores of every beam as well
+            self.lens_host = torch.empty(cap, beam_width, dtype=torch.int32).pin_memory()
+            self.scores_host = torch.empty(cap, beam_width, dtype=torch.float32).pin_memory()
         self.ids_dev: Optional[torch.Tensor] = None
         self.counts: List[int] = []
         self.rows = 0
@@ -90,13 +93,16 @@ class TraceCaptionPipeline:
     A model with a ViECap head (greedy search) is pipelined too: stage 1 runs the mapping network, the entity probabilities and the
     hard prompt composed on the device (each batch is one caption call, padded to its own longest prompt), stage 2 ONE ragged decode
     of ``viecap`` 64 steps for the group, every row at its own prompt length.  Captions come back per batch exactly as ``forward``
-    returns them.  Beam search raises ValueError, ``BoxRegions`` NotImplementedError."""
+    returns them.  A beam-search head is pipelined with ``beam_search=True`` (stage 2: one batched beam search of the group,
+    Engine.viecap_beam_ragged; a group then holds at most min(max_prefixes, 128) // beam_width images); without it, ValueError.
+    ``BoxRegions`` raises NotImplementedError."""
 
     viecap = None                         # the model's ViECap head, if it has one (set in __init__)
 
     def __init__(self, model, group_batches: int = 4, use_attention_tracing: bool = False, steps: int = 30,
                  stage_replicas: Sequence = (), stage_cus: Optional[int] = None, decode_cus: Optional[int] = None,
-                 vit_batches: int = 1, decode_replicas: Sequence = (), decode_clones: int = 0, eager_first: bool = False):
+                 vit_batches: int = 1, decode_replicas: Sequence = (), decode_clones: int = 0, eager_first: bool = False,
+                 beam_search: bool = False):
         """``stage_replicas``: further Patchioner instances holding the SAME weights (each has its own ViT
         workspace); stage 1 of consecutive batches then alternates over the replicas, each on its own stream,
         so that one batch's GEMM tails, epilogues and launch gaps are filled by the other's kernels."""
@@ -104,9 +110,20 @@ class TraceCaptionPipeline:
         self.stage_models = [model] + list(stage_replicas)
         self.viecap = getattr(model, "viecap", None)
         viecap_shape = None
+        self.beam_width = 0                        # > 0: the ViECap head's beam search (beam_search=True)
+        cap = self.eng.max_prefixes
         if self.viecap is not None:
+            if not self.viecap.args.using_greedy_search:
+                if not beam_search:
+                    raise ValueError("the ViECap head uses beam search (viecap.using_greedy_search=False): pass beam_search=True to "
+                                     "pipeline it")
+                self.beam_width = int(self.viecap.args.beam_width)
+                cap = min(self.eng.max_prefixes, 128) // self.beam_width     # images of one batched beam search
+                if int(group_batches) > cap:
+                    raise ValueError("group_batches = %d: a beam-search group holds at most min(max_prefixes, 128) // beam_width = "
+                                     "min(%d, 128) // %d = %d images" % (group_batches, self.eng.max_prefixes, self.beam_width, cap))
             for sm in self.stage_models:
-                sm.viecap.check_device_path()      # beam search / a hard prompt that does not decompose: ValueError
+                sm.viecap.check_device_path()      # a hard prompt that does not decompose: ValueError
             steps = self.viecap.steps              # greedy_search's 64 steps, whatever the DeCap default says
             viecap_shape = self.viecap.prompt_shape() + (int(self.eng.cfg.dec_embd),)
         # ``decode_replicas``: further instances (same weights, own decoder workspace) so that consecutive groups'
@@ -150,8 +167,8 @@ class TraceCaptionPipeline:
         self.sb = self.decode_streams[0]
         self._ndecoded = 0
         self._nstaged = 0
-        cap = self.eng.max_prefixes
-        self.groups = [_Group(cap, self.eng.prefix_size, steps, self.eng.device, viecap_shape) for _ in range(1 + len(self.decode_engines))]
+        self.groups = [_Group(cap, self.eng.prefix_size, steps, self.eng.device, viecap_shape, self.beam_width)
+                       for _ in range(1 + len(self.decode_engines))]
         self.last_ids: Optional[torch.Tensor] = None
 
     def _concurrent_streams(self, n: int, priority: int = 0, candidates: int = 16, beside: Sequence = ()) -> List[torch.cuda.Stream]:
@@ -354,7 +371,14 @@ class TraceCaptionPipeline:
             for ev in g.staged:
                 sb.wait_event(ev)
             g.staged = []
-            if self.viecap is not None:
+            if self.beam_width:
+                ids, lens, scores = eng.viecap_beam_ragged(g.cont[:g.rows] if g.cont is not None else None,
+                                                           g.tokens[:g.rows] if g.tokens is not None else None,
+                                                           g.lens[:g.rows] if g.lens is not None else None, self.beam_width,
+                                                           self.viecap.eos, soft_first=self.viecap.soft_first(), steps=self.steps)
+                g.lens_host[:g.rows].copy_(lens, non_blocking=True)
+                g.scores_host[:g.rows].copy_(scores, non_blocking=True)
+            elif self.viecap is not None:
                 ids = eng.viecap_decode_ragged(g.cont[:g.rows] if g.cont is not None else None,
                                                g.tokens[:g.rows] if g.tokens is not None else None,
                                                g.lens[:g.rows] if g.lens is not None else None,
@@ -373,6 +397,10 @@ class TraceCaptionPipeline:
         out, s = [], 0
         for n, nb in g.counts:
             k = n if nb is None else n * nb
+            if self.beam_width:                            # as VieCapHead.forward returns them: one text per image
+                out.append(self.viecap.beam_captions(rows[s:s + k], g.lens_host[s:s + k].tolist(), g.scores_host[s:s + k].tolist()))
+                s += k
+                continue
             if self.viecap is not None:                    # as VieCapHead.forward returns them (a batch of one: a str)
                 out.append(self.viecap.captions(rows[s:s + k]))
                 s += k

@@ -322,9 +322,7 @@ class VieCapHead:
                     self.fragments.to(self.device)
 
     def check_device_path(self) -> None:
-        """Raises unless this head can run enqueue-only (``enqueue``): greedy search, and a hard prompt that decomposes into fragments."""
-        if not self.args.using_greedy_search:
-            raise ValueError("the device path of the ViECap head is greedy search only (viecap.using_greedy_search=False: beam search)")
+        """Raises unless this head can run enqueue-only (``enqueue``): greedy or beam search, and a hard prompt that decomposes into fragments."""
         if self.args.using_hard_prompt:
             if self.fragments is None:
                 raise ValueError(self.fragment_error)
@@ -369,14 +367,21 @@ class VieCapHead:
     def soft_first(self) -> bool:
         return bool(self.args.soft_prompt_first) or not self.args.using_hard_prompt
 
-    def enqueue(self, image_features: torch.Tensor) -> torch.Tensor:
-        """``forward`` up to the greedy ids [N, 64] (device), for a greedy head, without a host copy or a sync: ``stage`` + the ragged
-        prompted decode (each row at its call's padded prompt length, which only the device knows).  ``captions(ids.tolist())`` then
-        gives what ``forward`` returns."""
+    def enqueue(self, image_features: torch.Tensor):
+        """``forward`` up to the device results, without a host copy or a sync: ``stage`` + the ragged prompted decode (each row at its
+        call's padded prompt length, which only the device knows).  Greedy head: the ids [N, 64]; ``captions(ids.tolist())`` then gives
+        what ``forward`` returns.  Beam head: (ids [N, W, 64], lens [N, W], scores [N, W]) of Engine.viecap_beam_ragged;
+        ``beam_captions`` of their host copies gives what ``forward`` returns (``last_ids`` stays None, as in ``forward``)."""
         self.check_device_path()
         if not isinstance(image_features, torch.Tensor):
             image_features = torch.tensor(image_features, dtype=torch.float)
         cont, tokens, lens = self.stage(image_features)
+        if not self.args.using_greedy_search:
+            if cont is None and tokens is None:
+                raise ValueError("viecap: neither a soft prompt nor a hard prompt")
+            self.last_ids = None
+            return self.engine.viecap_beam_ragged(cont, tokens, lens, int(self.args.beam_width), self.eos,
+                                                  soft_first=self.soft_first(), steps=self.steps)
         if tokens is None:
             ids = self.engine.viecap_decode(cont, None, soft_first=True, steps=self.steps)   # no hard prompt: forward's own call
         else:
@@ -404,6 +409,20 @@ class VieCapHead:
                     i = j
                     break
             out.append(self.tokenizer.decode(r[:i + 1]))
+        return out
+
+    @staticmethod
+    def beam_order(scores) -> List[int]:
+        """The beams best first, as beam_search ranks them (search.py:281-284): torch's descending argsort of the final fp32 scores.
+        One helper for the host loop and the device path, so that ties come out in the same order."""
+        return torch.as_tensor(scores, dtype=torch.float32).argsort(descending=True).tolist()
+
+    def beam_captions(self, ids, lens, scores) -> List[str]:
+        """Host copies of a beam head's device results (``enqueue``) -> what ``forward`` returns: every image's best beam's text."""
+        out = []
+        for row_ids, row_lens, row_scores in zip(ids, lens, scores):
+            b = self.beam_order(row_scores)[0]
+            out.append(self.tokenizer.decode(list(row_ids[b][:int(row_lens[b])])))
         return out
 
     def forward(self, image_features: torch.Tensor, compute_scores: bool = False):
@@ -486,7 +505,7 @@ class VieCapHead:
             is_stopped = is_stopped | (next_tokens == eos[0]) | (next_tokens == eos[1])
         scores = (scores / seq_lengths).astype(np.float32)
         texts = [self.tokenizer.decode(t[:int(n)]) for t, n in zip(tokens, seq_lengths)]
-        order = torch.from_numpy(scores).argsort(descending=True).tolist()
+        order = self.beam_order(scores)
         self.last_beams = [(tokens[b][:int(seq_lengths[b])], float(seq_lengths[b]), float(scores[b])) for b in range(W)]
         self.last_beam_order = order
         return [texts[b] for b in order]
