@@ -381,6 +381,51 @@ int pio_host_interpolate_pos_embed_plain(const float* pos, int32_t grid, int32_t
 int pio_host_pil_ksize(int32_t in_size, int32_t out_size);
 int pio_host_pil_table(int32_t in_size, int32_t out_size, int32_t first, int32_t count, int32_t* kk, int32_t* bounds);
 
+/* ---- Test hooks: the ViT block kernels one at a time, for the kernel-by-kernel tests.  Caller-owned DEVICE pointers (torch
+ *      tensors' data_ptr()), the current HIP device, no pio_handle.  Every size is validated before anything is launched; a refused
+ *      call returns PIO_ERR_INVALID_ARG (or PIO_ERR_HIP with the HIP error) with pio_last_error() set and launches nothing.
+ *      Buffer extents cannot be checked: they are the caller's (the shapes below). */
+enum {
+  PIO_GEMM_EPI_PATCH_EMBED = 0,  /* x[b*Tp + G + p][n] = acc + bias[n] + pos[1 + p][n]      (fp32; p = m mod n2, b = m / n2) */
+  PIO_GEMM_EPI_QKV = 1,          /* q, k [B][H][Tk][64], vT [B][H][64][Tk] (operand type; rows m = b*Tp + t) (+ qkv_last [B][T][3D] fp32) */
+  PIO_GEMM_EPI_RESIDUAL = 2,     /* x[m][n] = old x joined into the sum + bias[n]                 (fp32, in place) */
+  PIO_GEMM_EPI_GELU = 3          /* out16[m][n] = GELU(acc + bias[n]): act 0 exact erf, 1 QuickGELU (operand type) */
+};
+enum {
+  PIO_GEMM_PATH_AUTO = 0,        /* what the forward passes take (the dispatch by tile count) */
+  PIO_GEMM_PATH_NARROW = 1,      /* 128-wide kernel, 64-row tiles, three buffers: patch embed, residual */
+  PIO_GEMM_PATH_RES128 = 2,      /* 128-wide kernel, 128-row tiles, two buffers, lazy x join: residual, K / 64 >= 10 */
+  PIO_GEMM_PATH_WIDE128 = 3,     /* 128-wide kernel, 128-row tiles, one buffer: qkv, GELU */
+  PIO_GEMM_PATH_K256 = 4,        /* 256 x 256 kernel: patch embed, qkv, GELU */
+  PIO_GEMM_PATH_ROLL = 5         /* persistent rolling kernel: qkv without capture (Tp >= 256), GELU (Tp >= 256), residual (K / 64 >= 12) */
+};
+typedef struct {
+  const void* A;          /* [M][lda] operand type */
+  const void* W;          /* [N][K] operand type */
+  const float* bias;      /* [N] */
+  int32_t M, N, K, lda;
+  float* x;               /* PATCH_EMBED: [B*Tp][D] (written); RESIDUAL: [M][N] (read and written) */
+  const float* pos;       /* PATCH_EMBED: [1 + n2][D] */
+  void* out16;            /* GELU: [M][N] */
+  void* q; void* k; void* vT;
+  float* qkv_last;        /* QKV: optional fp32 capture [B][T][3D] (NULL: none) */
+  int32_t T, Tp, Tk, G, n2, D, H, act;
+  const void* pf;         /* optional: bytes the extra cache-warming workgroups read (never written) */
+  int32_t pf_bytes;
+} pio_test_gemm_args;
+/* operand 0 = fp16, 1 = bf16; *path_taken (may be NULL) = the PIO_GEMM_PATH_* that ran */
+int pio_test_vit_gemm(int32_t operand, int32_t epi, int32_t path, const pio_test_gemm_args* args, int32_t* path_taken, pio_stream stream);
+/* host only: the PIO_GEMM_PATH_* PIO_GEMM_PATH_AUTO takes for these sizes, PIO_ERR_INVALID_ARG where no kernel takes them */
+int pio_test_gemm_route(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t D, int32_t Tp, int32_t has_capture);
+/* kind 0: the ViT flash attention (lens: optional DEVICE [B], 1 <= lens[b] <= T: keys >= lens[b] masked); kind 1: the text tower's
+ * causal attention (keys <= query; T, lens unused).  q, k [B][H][Tk][64], vT [B][H][64][Tk] -> out [B*Tp][D], operand type. */
+int pio_test_attention(int32_t kind, int32_t operand, const void* q, const void* k, const void* vT, void* out, int32_t B, int32_t H,
+                       int32_t T, int32_t Tp, int32_t Tk, int32_t D, float scale, const int32_t* lens, pio_stream stream);
+/* LayerNorm rows of x [M][D] fp32 (D % 4 == 0, D <= 1024): out16 [M][D] operand type, or (out16 NULL) out32 fp32 with the rows
+ * t >= T of every Tp-row image dropped ([M / Tp * T][D]) */
+int pio_test_layernorm(int32_t operand, const float* x, const float* w, const float* b, float eps, int32_t M, int32_t D, void* out16,
+                       float* out32, int32_t T, int32_t Tp, pio_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,16 @@ class PioTextConfig(ctypes.Structure):
     ]
 
 
+class PioTestGemmArgs(ctypes.Structure):
+    """pio_test_gemm_args (the test hooks' mirror of the GEMM launch arguments)."""
+    _fields_ = [
+        ("A", c_void_p), ("W", c_void_p), ("bias", c_void_p), ("M", c_int32), ("N", c_int32), ("K", c_int32), ("lda", c_int32),
+        ("x", c_void_p), ("pos", c_void_p), ("out16", c_void_p), ("q", c_void_p), ("k", c_void_p), ("vT", c_void_p),
+        ("qkv_last", c_void_p), ("T", c_int32), ("Tp", c_int32), ("Tk", c_int32), ("G", c_int32), ("n2", c_int32), ("D", c_int32),
+        ("H", c_int32), ("act", c_int32), ("pf", c_void_p), ("pf_bytes", c_int32),
+    ]
+
+
 # every symbol include/patchioner_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "pio_last_error": (c_char_p, []),
@@ -113,6 +123,12 @@ SIGNATURES = {
     "pio_host_interpolate_pos_embed_plain": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_double, c_void_p]),
     "pio_host_pil_ksize": (c_int32, [c_int32, c_int32]),
     "pio_host_pil_table": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "pio_test_vit_gemm": (c_int32, [c_int32, c_int32, c_int32, POINTER(PioTestGemmArgs), POINTER(c_int32), c_void_p]),
+    "pio_test_gemm_route": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "pio_test_attention": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                     c_int32, c_int32, c_float, c_void_p, c_void_p]),
+    "pio_test_layernorm": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                     c_int32, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

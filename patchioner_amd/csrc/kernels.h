@@ -70,6 +70,14 @@ __host__ __device__ constexpr int resid_class(int m, int n) { return (m & 3) + 4
 __host__ __device__ constexpr int resid_join_ktile(int e, int nk) { return e + 1 < nk - 1 ? e + 1 : nk - 1; }
 
 hipError_t launch_vit_gemm(OperandType t, GemmEpilogue epi, const GemmArgs& a, hipStream_t s);
+// The kernels launch_vit_gemm chooses between (values = PIO_GEMM_PATH_* of the C ABI's test hooks):  NARROW = k_vit_gemm with 64-row
+// tiles (patch embed, proj / fc2), RES128 = its 128-row two-buffer residual form (lazy x join), WIDE128 = its 128-row form of qkv / fc1,
+// K256 = k_vit_gemm256, ROLL = k_vit_gemm_roll.  launch_vit_gemm == launch_vit_gemm_path(route_vit_gemm(epi, a)); route_vit_gemm is
+// host only and returns -1 where no kernel takes the GEMM.  An explicit path launches only a kernel instantiated for the epilogue whose
+// preconditions hold, else hipErrorInvalidValue (nothing launched).
+enum GemmPath { GEMM_AUTO = 0, GEMM_NARROW = 1, GEMM_RES128 = 2, GEMM_WIDE128 = 3, GEMM_K256 = 4, GEMM_ROLL = 5 };
+int route_vit_gemm(GemmEpilogue epi, const GemmArgs& a);
+hipError_t launch_vit_gemm_path(OperandType t, GemmEpilogue epi, GemmPath p, const GemmArgs& a, hipStream_t s);
 // 256 x 256 tiles, 8 waves (vit_gemm256.hip): same arithmetic per output element; launch_vit_gemm dispatches to it
 bool vit_gemm256_fits(GemmEpilogue epi, const GemmArgs& a);
 hipError_t launch_vit_gemm256(OperandType t, GemmEpilogue epi, const GemmArgs& a, hipStream_t s);

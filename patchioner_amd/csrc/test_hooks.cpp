@@ -1,0 +1,134 @@
+// C ABI test hooks (include/patchioner_hip.h, "Test hooks"): one ViT block kernel per call on caller-owned device buffers, for the
+// kernel-by-kernel tests.  A translation unit of its own: api.cpp's host side (tests/test_asan_host.py) does not link the kernels' launchers.
+#include "../../include/patchioner_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "common.h"
+#include "kernels.h"
+
+using namespace pio;
+
+namespace pio {
+int api_fail(int code, const std::string& msg);   // api.cpp: sets pio_last_error's message
+}  // namespace pio
+
+namespace {
+
+int fail(int code, const std::string& msg) { return api_fail(code, msg); }
+
+GemmArgs test_gemm_args(const pio_test_gemm_args& t) {
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A = t.A; g.W = t.W; g.bias = t.bias; g.M = t.M; g.N = t.N; g.K = t.K; g.lda = t.lda;
+  g.x = t.x; g.pos = t.pos; g.out16 = t.out16; g.q = t.q; g.k = t.k; g.vT = t.vT; g.qkv_last = t.qkv_last;
+  g.T = t.T; g.Tp = t.Tp; g.Tk = t.Tk; g.G = t.G; g.n2 = t.n2; g.D = t.D; g.H = t.H; g.act = t.act;
+  g.pf = t.pf; g.pf_bytes = t.pf_bytes;
+  return g;
+}
+
+// the sizes every kernel of the epilogue relies on (the forward passes hold them by construction); "" when they hold
+std::string test_gemm_shape_error(int32_t epi, const pio_test_gemm_args& t, bool route_only) {
+  if (t.M < 1 || t.N < 1 || t.K < 1 || t.lda < t.K || t.lda % 8 != 0) return "M, N, K >= 1, lda >= K, lda % 8 == 0";
+  if (!route_only && (!t.A || !t.W || !t.bias)) return "null A, W or bias";
+  if (!route_only && (t.pf_bytes < 0 || (t.pf_bytes > 0 && !t.pf))) return "pf_bytes > 0 needs pf";
+  switch (epi) {
+    case PIO_GEMM_EPI_PATCH_EMBED:
+      if (t.N != t.D || t.n2 < 1 || t.M % t.n2 != 0 || t.G < 0 || t.Tp < t.G + t.n2) return "patch embed: N == D, M % n2 == 0, Tp >= G + n2";
+      if (!route_only && (!t.x || !t.pos)) return "patch embed: null x or pos";
+      return "";
+    case PIO_GEMM_EPI_QKV:
+      if (t.H < 1 || t.D != 64 * t.H || t.D % 128 != 0 || t.N != 3 * t.D) return "qkv: D == 64 H, D % 128 == 0, N == 3 D";
+      if (t.Tp < 8 || t.Tp % 8 != 0 || t.M % t.Tp != 0 || t.Tk < t.Tp || t.Tk % 8 != 0) return "qkv: Tp % 8 == 0, M % Tp == 0, Tk >= Tp, Tk % 8 == 0";
+      if (t.qkv_last && (t.T < 1 || t.T > t.Tp)) return "qkv: capture needs 1 <= T <= Tp";
+      if (!route_only && (!t.q || !t.k || !t.vT)) return "qkv: null q, k or vT";
+      return "";
+    case PIO_GEMM_EPI_RESIDUAL:
+      if (t.N != t.D) return "residual: N == D";
+      if (!route_only && !t.x) return "residual: null x";
+      return "";
+    case PIO_GEMM_EPI_GELU:
+      if (t.act != 0 && t.act != 1) return "gelu: act 0 or 1";
+      if (!route_only && !t.out16) return "gelu: null out16";
+      return "";
+  }
+  return "epi outside 0..3";
+}
+
+}  // namespace
+
+extern "C" {
+
+int pio_test_vit_gemm(int32_t operand, int32_t epi, int32_t path, const pio_test_gemm_args* args, int32_t* path_taken, pio_stream stream) {
+  if (path_taken) *path_taken = -1;
+  if (!args) return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_gemm: null args");
+  if (operand != 0 && operand != 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_gemm: operand 0 (fp16) or 1 (bf16)");
+  if (path < PIO_GEMM_PATH_AUTO || path > PIO_GEMM_PATH_ROLL) return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_gemm: path outside 0..5");
+  const std::string err = test_gemm_shape_error(epi, *args, false);
+  if (!err.empty()) return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_gemm: " + err);
+  const GemmArgs g = test_gemm_args(*args);
+  const int p = path == PIO_GEMM_PATH_AUTO ? route_vit_gemm((GemmEpilogue)epi, g) : path;
+  if (p < 0) return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_gemm: no kernel takes these sizes");
+  const hipError_t e = launch_vit_gemm_path(operand == 1 ? OP_BF16 : OP_F16, (GemmEpilogue)epi, (GemmPath)p, g, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_gemm: path " + std::to_string(p) + " refuses epilogue " + std::to_string(epi) +
+                                         " at M " + std::to_string(g.M) + ", N " + std::to_string(g.N) + ", K " + std::to_string(g.K));
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_vit_gemm: ") + hipGetErrorString(e));
+  if (path_taken) *path_taken = p;
+  return PIO_OK;
+}
+
+int pio_test_gemm_route(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t D, int32_t Tp, int32_t has_capture) {
+  pio_test_gemm_args t;
+  memset(&t, 0, sizeof(t));
+  t.M = M; t.N = N; t.K = K; t.lda = lda; t.D = D; t.Tp = Tp; t.T = Tp; t.Tk = round_up(Tp, 64); t.H = D / 64; t.act = 0;
+  t.n2 = 1; t.G = 0;                                          // the route does not depend on the image layout
+  t.qkv_last = has_capture ? (float*)&t : nullptr;        // only its presence is read
+  const std::string err = test_gemm_shape_error(epi, t, true);
+  if (!err.empty()) return fail(PIO_ERR_INVALID_ARG, "pio_test_gemm_route: " + err);
+  const int p = route_vit_gemm((GemmEpilogue)epi, test_gemm_args(t));
+  if (p < 0) return fail(PIO_ERR_INVALID_ARG, "pio_test_gemm_route: no kernel takes these sizes");
+  return p;
+}
+
+int pio_test_attention(int32_t kind, int32_t operand, const void* q, const void* k, const void* vT, void* out, int32_t B, int32_t H,
+                       int32_t T, int32_t Tp, int32_t Tk, int32_t D, float scale, const int32_t* lens, pio_stream stream) {
+  if (kind != 0 && kind != 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_attention: kind 0 (ViT) or 1 (text, causal)");
+  if (operand != 0 && operand != 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_attention: operand 0 (fp16) or 1 (bf16)");
+  if (!q || !k || !vT || !out) return fail(PIO_ERR_INVALID_ARG, "pio_test_attention: null buffer");
+  if (B < 1 || H < 1 || D != 64 * H || Tp < 1 || Tp % 8 != 0 || Tk < Tp || !(scale > 0.f) || !std::isfinite(scale))
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_attention: B, H >= 1, D == 64 H, Tp % 8 == 0, Tk >= Tp, finite scale > 0");
+  if (kind == 0 && (T < 1 || T > Tp || Tk % 64 != 0))
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_attention: ViT attention needs 1 <= T <= Tp and Tk % 64 == 0");
+  if (kind == 1 && (lens || round_up(Tp, 32) > 128 || Tk < round_up(Tp, 32) || Tk % 8 != 0))
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_attention: text attention needs no lens, round_up(Tp, 32) <= min(Tk, 128), Tk % 8 == 0");
+  VitAttnArgs a;
+  a.q = q; a.k = k; a.vT = vT; a.out = out; a.B = B; a.H = H; a.T = kind == 0 ? T : Tp; a.Tp = Tp; a.Tk = Tk; a.D = D; a.scale = scale;
+  a.lens = kind == 0 ? lens : nullptr;
+  const OperandType t = operand == 1 ? OP_BF16 : OP_F16;
+  const hipError_t e = kind == 0 ? launch_vit_attention(t, a, (hipStream_t)stream) : launch_text_attention(t, a, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_attention: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_attention: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_layernorm(int32_t operand, const float* x, const float* w, const float* b, float eps, int32_t M, int32_t D, void* out16,
+                       float* out32, int32_t T, int32_t Tp, pio_stream stream) {
+  if (operand != 0 && operand != 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_layernorm: operand 0 (fp16) or 1 (bf16)");
+  if (!x || !w || !b || (out16 == nullptr) == (out32 == nullptr))
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_layernorm: x, w, b and exactly one of out16 / out32");
+  if (M < 1 || D < 4 || D % 4 != 0 || D > 1024 || !(eps > 0.f))
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_layernorm: M >= 1, D % 4 == 0, 4 <= D <= 1024, eps > 0");
+  if (out32 && (Tp < 1 || T < 1 || T > Tp || M % Tp != 0))
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_layernorm: out32 needs 1 <= T <= Tp and M % Tp == 0");
+  const hipError_t e = launch_layernorm(operand == 1 ? OP_BF16 : OP_F16, x, w, b, eps, M, D, out16, out32, T, Tp, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_layernorm: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_layernorm: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+}  // extern "C"

@@ -412,27 +412,58 @@ static hipError_t launch_one(const GemmArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// The lazy x-join form (NBUF != 3 with EPI_RESIDUAL) joins class c of a column half after K-tile c + 1 + 4 (column half) and needs
+// every class on a K-tile of its own: nk >= 10.  Below, the classes past the last K-tile would never join and the old residual would be
+// dropped without a sign, so every launch of that form refuses it (a build with PIO_GEMM_NBUF_NARROW != 3 meets it at ViT-S proj, nk = 6).
+static constexpr int LAZY_MIN_NK = 10;
+template <int EPI, int NBUF>
+static bool lazy_join_ok(const GemmArgs& a) { return !(EPI == EPI_RESIDUAL && NBUF != 3) || a.K / BK >= LAZY_MIN_NK; }
+
+// the 128-wide kernel's own preconditions (every form)
+static bool gemm128_fits(GemmEpilogue epi, const GemmArgs& a) {
+  if (a.M <= 0 || a.N % BN != 0 || a.K % (2 * BK) != 0 || a.lda % 8 != 0) return false;
+  // the staging offsets are 32-bit byte offsets from A and W
+  if ((size_t)a.M * a.lda * 2 >= ((size_t)1 << 32) || (size_t)a.N * a.K * 2 >= ((size_t)1 << 32)) return false;
+  if (epi == EPI_RESIDUAL && (size_t)a.M * a.N >= ((size_t)1 << 30)) return false;      // 32-bit element index into x
+  return true;
+}
+
+// 32 images and more per launch (the pipeline's shared ViT launches): 128-row tiles fill the chip on their own (>= 1.5 workgroups
+// per CU) and halve the W re-reads: 2.90 vs 3.21 ms per 32-image forward.  Same k order per element, so the result does not depend
+// on the tile height.
+static bool res128_wanted(const GemmArgs& a) {
+  static const int force_bm = [] { const char* e = getenv("PIO_GEMM_RES_BM"); return e ? atoi(e) : 0; }();   // diagnostic: 64 / 128
+  return a.K / BK >= LAZY_MIN_NK && (force_bm == 128 || (force_bm == 0 && ceil_div(a.M, 128) * (a.N / BN) >= 384));
+}
+
+// one form of k_vit_gemm, chosen by the caller; a form not instantiated for the epilogue, or whose preconditions fail, is refused
 template <typename T>
-static hipError_t launch_typed(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
-  switch (epi) {
-    case EPI_PATCH_EMBED: return launch_one<T, EPI_PATCH_EMBED, PIO_GEMM_BM_NARROW, PIO_GEMM_NBUF_NARROW>(a, s);
-    case EPI_QKV:
-      if constexpr (PIO_GEMM_BM_BIG != 0) { if (a.M >= PIO_GEMM_BIG_M) return launch_one<T, EPI_QKV, PIO_GEMM_BM_BIG == 0 ? 128 : PIO_GEMM_BM_BIG, PIO_GEMM_NBUF_BIG>(a, s); }
-      return launch_one<T, EPI_QKV, 128, PIO_GEMM_NBUF_WIDE>(a, s);
-    case EPI_RESIDUAL:
-      // 32 images and more per launch (the pipeline's shared ViT launches): 128-row tiles fill the chip on their own
-      // (>= 1.5 workgroups per CU) and halve the W re-reads: 2.90 vs 3.21 ms per 32-image forward.  Same k order per
-      // element, so the result does not depend on the tile height.
-      {
-        static const int force_bm = [] { const char* e = getenv("PIO_GEMM_RES_BM"); return e ? atoi(e) : 0; }();   // diagnostic: 64 / 128
-        if (a.K / BK >= 10 && (force_bm == 128 || (force_bm == 0 && ceil_div(a.M, 128) * (a.N / BN) >= 384))) return launch_one<T, EPI_RESIDUAL, 128, 2>(a, s);
+static hipError_t launch_typed(GemmEpilogue epi, GemmPath p, const GemmArgs& a, hipStream_t s) {
+  if (!gemm128_fits(epi, a)) return hipErrorInvalidValue;
+  switch (p) {
+    case GEMM_NARROW:
+      if (epi == EPI_PATCH_EMBED) return launch_one<T, EPI_PATCH_EMBED, PIO_GEMM_BM_NARROW, PIO_GEMM_NBUF_NARROW>(a, s);
+      if (epi == EPI_RESIDUAL) {
+        if (!lazy_join_ok<EPI_RESIDUAL, PIO_GEMM_NBUF_NARROW>(a)) return hipErrorInvalidValue;
+        return launch_one<T, EPI_RESIDUAL, PIO_GEMM_BM_NARROW, PIO_GEMM_NBUF_NARROW>(a, s);
       }
-      return launch_one<T, EPI_RESIDUAL, PIO_GEMM_BM_NARROW, PIO_GEMM_NBUF_NARROW>(a, s);
-    case EPI_GELU:
-      if constexpr (PIO_GEMM_BM_BIG != 0) { if (a.M >= PIO_GEMM_BIG_M) return launch_one<T, EPI_GELU, PIO_GEMM_BM_BIG == 0 ? 128 : PIO_GEMM_BM_BIG, PIO_GEMM_NBUF_BIG>(a, s); }
-      return launch_one<T, EPI_GELU, 128, PIO_GEMM_NBUF_WIDE>(a, s);
+      return hipErrorInvalidValue;
+    case GEMM_RES128:
+      if (epi != EPI_RESIDUAL || !lazy_join_ok<EPI_RESIDUAL, 2>(a)) return hipErrorInvalidValue;
+      return launch_one<T, EPI_RESIDUAL, 128, 2>(a, s);
+    case GEMM_WIDE128:
+      if (epi == EPI_QKV) {
+        if constexpr (PIO_GEMM_BM_BIG != 0) { if (a.M >= PIO_GEMM_BIG_M) return launch_one<T, EPI_QKV, PIO_GEMM_BM_BIG == 0 ? 128 : PIO_GEMM_BM_BIG, PIO_GEMM_NBUF_BIG>(a, s); }
+        return launch_one<T, EPI_QKV, 128, PIO_GEMM_NBUF_WIDE>(a, s);
+      }
+      if (epi == EPI_GELU) {
+        if constexpr (PIO_GEMM_BM_BIG != 0) { if (a.M >= PIO_GEMM_BIG_M) return launch_one<T, EPI_GELU, PIO_GEMM_BM_BIG == 0 ? 128 : PIO_GEMM_BM_BIG, PIO_GEMM_NBUF_BIG>(a, s); }
+        return launch_one<T, EPI_GELU, 128, PIO_GEMM_NBUF_WIDE>(a, s);
+      }
+      return hipErrorInvalidValue;
+    default:
+      return hipErrorInvalidValue;
   }
-  return hipErrorInvalidValue;
 }
 
 // The 256 x 256 kernel (vit_gemm256.hip) takes a GEMM over once it has enough 256-tiles to occupy the chip: measured
@@ -474,22 +505,41 @@ static int gemm_rres_min_tiles() {
   return v;
 }
 
-hipError_t launch_vit_gemm(OperandType t, GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
+int route_vit_gemm(GemmEpilogue epi, const GemmArgs& a) {
   if (epi == EPI_RESIDUAL) {
     if (gemm_rres_min_tiles() > 0 && a.M > 0 && a.N % 256 == 0 && ceil_div(a.M, 256) * (a.N / 256) >= gemm_rres_min_tiles() &&
         vit_gemm_roll_fits(epi, a))
-      return launch_vit_gemm_roll(t, epi, a, s);
+      return GEMM_ROLL;
   } else
   if (gemm_roll_min_tiles() > 0 && a.M > 0 && a.N % 256 == 0 && ceil_div(a.M, 256) * (a.N / 256) >= gemm_roll_min_tiles() &&
       vit_gemm_roll_fits(epi, a))
-    return launch_vit_gemm_roll(t, epi, a, s);
+    return GEMM_ROLL;
   if (gemm256_min_tiles() > 0 && a.M > 0 && a.N % 256 == 0 && gemm256_wanted(epi, a) && vit_gemm256_fits(epi, a))
-    return launch_vit_gemm256(t, epi, a, s);
-  if (a.M <= 0 || a.N % BN != 0 || a.K % (2 * BK) != 0 || a.lda % 8 != 0) return hipErrorInvalidValue;
-  // the staging offsets are 32-bit byte offsets from A and W
-  if ((size_t)a.M * a.lda * 2 >= ((size_t)1 << 32) || (size_t)a.N * a.K * 2 >= ((size_t)1 << 32)) return hipErrorInvalidValue;
-  if (epi == EPI_RESIDUAL && (size_t)a.M * a.N >= ((size_t)1 << 30)) return hipErrorInvalidValue;      // 32-bit element index into x
-  return t == OP_F16 ? launch_typed<f16>(epi, a, s) : launch_typed<bf16>(epi, a, s);
+    return GEMM_K256;
+  if (!gemm128_fits(epi, a)) return -1;
+  switch (epi) {
+    case EPI_PATCH_EMBED: return GEMM_NARROW;
+    case EPI_RESIDUAL: return res128_wanted(a) ? GEMM_RES128 : GEMM_NARROW;
+    case EPI_QKV: case EPI_GELU: return GEMM_WIDE128;
+  }
+  return -1;
+}
+
+hipError_t launch_vit_gemm_path(OperandType t, GemmEpilogue epi, GemmPath p, const GemmArgs& a, hipStream_t s) {
+  switch (p) {
+    case GEMM_AUTO: return launch_vit_gemm(t, epi, a, s);
+    case GEMM_ROLL: return launch_vit_gemm_roll(t, epi, a, s);
+    case GEMM_K256: return launch_vit_gemm256(t, epi, a, s);
+    case GEMM_NARROW: case GEMM_RES128: case GEMM_WIDE128:
+      return t == OP_F16 ? launch_typed<f16>(epi, p, a, s) : launch_typed<bf16>(epi, p, a, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_vit_gemm(OperandType t, GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
+  const int p = route_vit_gemm(epi, a);
+  if (p < 0) return hipErrorInvalidValue;
+  return launch_vit_gemm_path(t, epi, (GemmPath)p, a, s);
 }
 
 }  // namespace pio
