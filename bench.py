@@ -1,7 +1,12 @@
 """Headline benchmark: captions/s of the Patch-ioner hot path on MI355X (BASELINE.json config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line (`value`, `ms_per_step`,
+`config`) and nothing else.  --full adds what takes runs of its own after the timed steps: the per-group statistics, the
+synchronous forward, the HIP-event stage breakdown and rooflines, the 160-images-per-launch pipeline, the preprocessing
+figure, BASELINE configs 3 / 4 / 5 and the CPU baseline (the last two at N = 1; --no-configs / --no-cpu-baseline drop them).
 
 Both forms work for N > 1: started without a torch.distributed.run environment, ``bench.py --gpus N`` spawns its N ranks
 itself (fresh child processes through ``python -m torch.distributed.run``, before anything in the parent touches the GPU)
@@ -326,12 +331,15 @@ def main():
     ap.add_argument("--steps", type=int, default=128,
                     help="timed steps (16 groups of 8 batches by default: the pipeline's fill and drain, about 5 ms, are inside the timed region)")
     ap.add_argument("--warmup", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the records of BASELINE configs 3 / 4 / 5 (`configs` in the line; ~40 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline (statistics, synchronous forward, "
+                         "rooflines, 160-image launches, preprocessing, configs 3 / 4 / 5, CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (`cpu_baseline` in the line)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the records of BASELINE configs 3 / 4 / 5 (`configs` in the line; ~40 s)")
     ap.add_argument("--in-flight", type=int, default=int(os.environ.get("PIO_BENCH_IN_FLIGHT", "8")),
                     help="batches per decode group (mode=group: stage 1 runs per bs-16 batch, ONE greedy decode serves "
                          "this many batches, <= 8 = 128 prefixes) or forwards in flight (mode=streams); 1 = the "
-                         "reference's synchronous forward, which is also always measured and reported as `sync`")
+                         "reference's synchronous forward, which --full also measures and reports as `sync`")
     ap.add_argument("--mode", choices=["group", "streams"], default=os.environ.get("PIO_BENCH_MODE", "group"))
     ap.add_argument("--stage-streams", type=int, default=int(os.environ.get("PIO_BENCH_STAGE_STREAMS", "1")),
                     help="mode=group: model replicas (own ViT workspace, own stream) that stage 1 alternates over")
@@ -437,6 +445,40 @@ def main():
     dt = time.perf_counter() - t0
     if args.dump_outputs and rank == 0:        # copied now: the later regions reuse the decode buffers that `ids` lives in
         dump_outputs(args.dump_outputs, outs, ids.cpu())
+    assert len(outs["trace_capts"]) == BATCH and ids.shape[0] == BATCH * world
+    if world > 1:
+        t = torch.tensor([dt], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else "cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t[0].item())
+    line = {
+        "metric": "captions/sec (whole node) + ms/image, ViT-B/14 224^2 bs16, 1/2/4/8 MI355X",
+        "value": BATCH * world * args.steps / dt, "unit": "captions/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "ms_per_image": dt / args.steps * 1e3 / BATCH,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp16", "data": "synthetic",
+        "value_api": ("TraceCaptionPipeline.run (pipeline.py): the same forward, batches staged %d per ViT launch and decoded %d "
+                      "per greedy decode; the reference's call pattern, one synchronous model.forward() per batch, is `forward_sync` (--full)"
+                      % (VB, P)) if pipe is not None else "Patchioner.forward, one synchronous call per batch",
+        "config": {"workload": ("config 2, bs16 traces; value: %d images per ViT launch, %d prefixes per decode (pipeline API); forward_sync: "
+                                "1 forward(16) per call. " % (BATCH * VB, BATCH * P) if pipe is not None else "config 2, bs16 traces, one forward(16) per step. ") +
+                               "talk2dino_decap_COCO, ViT-B/14-reg 224^2, batch 16/GPU, caption_from=patches "
+                               "(one 16-patch trace region per image), bank 591753x768 fp32, 30-step greedy decode; `value` is measured "
+                               "through the throughput API (value_api), the drop-in forward() figure is forward_sync (--full)",
+                   "env": {"HIP_FORCE_DEV_KERNARG": os.environ.get("HIP_FORCE_DEV_KERNARG")},
+                   "arithmetic": {"vit": "fp16 operands, fp32 accumulation (v_mfma_f32_32x32x16_f16), fp32 residual stream / LayerNorm",
+                                  "projection": "operands as fp16 hi + lo pairs (22 significant bits) on v_mfma_f32_16x16x32_f16, fp32 "
+                                                "accumulation and soft-max; as close to fp64 as an fp32 evaluation (DESIGN.md section 3)",
+                                  "decoder": "fp32 (v_mfma_f32_16x16x4_f32) at <= 64 prefixes per decode; above, the three wide layer GEMMs on fp16 hi + lo pairs (three v_mfma_f32_16x16x32_f16 per product, fp32 accumulation; same ids on every test); greedy ids through an fp16 filter + exact fp32 re-evaluation"},
+                   "global_batch": BATCH * world, "parallelism": "dp%d (image shards, ids all-gather)" % world, "batches_in_flight_per_gpu": P, "batches_per_vit_launch": VB, "concurrent_decodes": DS if args.mode == "group" else 1,
+                   "pipelining": "none" if P == 1 else ("one decode per %d batches (up to %d decodes in flight, one decoder clone and stream each), overlapped with the next batches' ViT (one launch per %d batches) on %d stream(s)" % (P, DS, VB, S)
+                                                       if args.mode == "group" else "%d forwards on %d streams" % (P, P))},
+    }
+    if not args.full:                          # the headline alone: nothing else runs on the GPU after the timed steps
+        if rank == 0:
+            print(json.dumps(line))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # Per-group statistics of the pipelined path over >= 100 groups (median + p95), outside the K timed steps:
     # the interval between consecutive groups' ids becoming available on the host.
     group_ms = []
@@ -551,7 +593,6 @@ def main():
         model.engine.profile_enable(False)
         del big
         big_launch = (dt10, prof10, prof10a)
-    assert len(outs["trace_capts"]) == BATCH and ids.shape[0] == BATCH * world
     # Image transforms (the reference times them apart from inference, eval_trace_captioning.py:233-262): 16 camera-sized
     # RGB images -> [16,3,224,224] on the device (pio_preprocess: raw pixels over PCIe, resize / crop / normalise on the
     # GPU, bit-exact to PIL) beside the host PIL transform of the mirror.  Not part of `value`.
@@ -582,9 +623,9 @@ def main():
         except ImportError:
             pass
     if world > 1:
-        t = torch.tensor([dt, dt_sync], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else "cuda")
+        t = torch.tensor([dt_sync], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, dt_sync = float(t[0].item()), float(t[1].item())
+        dt_sync = float(t[0].item())
     sync_stats = _stats(sync_ms)
     group_stats = _stats(group_ms) if group_ms else None
 
@@ -626,32 +667,12 @@ def main():
             stages[k] = {"ms_per_step": v["ms"] / prof_steps, "launches_per_step": v["launches"] / prof_steps,
                          "tflops": v["flops"] / sec / 1e12 if v["flops"] else None,
                          "gbs": v["bytes"] / sec / 1e9 if v["bytes"] else None}
-        line = {
-            "metric": "captions/sec (whole node) + ms/image, ViT-B/14 224^2 bs16, 1/2/4/8 MI355X",
-            "value": BATCH * world * args.steps / dt, "unit": "captions/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "ms_per_image": dt / args.steps * 1e3 / BATCH,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp16", "data": "synthetic",
-            "value_api": ("TraceCaptionPipeline.run (pipeline.py): the same forward, batches staged %d per ViT launch and decoded %d "
-                          "per greedy decode; the reference's call pattern, one synchronous model.forward() per batch, is `forward_sync`"
-                          % (VB, P)) if pipe is not None else "Patchioner.forward, one synchronous call per batch",
+        line.update({
             "forward_sync": {"value": BATCH * world * 1e3 / sync_stats["median"], "unit": "captions/s",
                              "ms_per_forward": sync_stats, "note": "SURVEY 8d's timed region: model.forward(imgs, traces=...) on "
                              "device-resident images, id->string included; %d calls, each timed" % sync_steps},
             "pipelined_groups": {"ms_per_group": group_stats, "batches_per_group": P,
                                  "captions_per_s_at_median": BATCH * P * world * 1e3 / group_stats["median"]} if group_stats else None,
-            "config": {"workload": ("config 2, bs16 traces; value: %d images per ViT launch, %d prefixes per decode (pipeline API); forward_sync: "
-                                    "1 forward(16) per call. " % (BATCH * VB, BATCH * P) if pipe is not None else "config 2, bs16 traces, one forward(16) per step. ") +
-                                   "talk2dino_decap_COCO, ViT-B/14-reg 224^2, batch 16/GPU, caption_from=patches "
-                                   "(one 16-patch trace region per image), bank 591753x768 fp32, 30-step greedy decode; `value` is measured "
-                                   "through the throughput API (value_api), the drop-in forward() figure is forward_sync",
-                       "env": {"HIP_FORCE_DEV_KERNARG": os.environ.get("HIP_FORCE_DEV_KERNARG")},
-                       "arithmetic": {"vit": "fp16 operands, fp32 accumulation (v_mfma_f32_32x32x16_f16), fp32 residual stream / LayerNorm",
-                                      "projection": "operands as fp16 hi + lo pairs (22 significant bits) on v_mfma_f32_16x16x32_f16, fp32 "
-                                                    "accumulation and soft-max; as close to fp64 as an fp32 evaluation (DESIGN.md section 3)",
-                                      "decoder": "fp32 (v_mfma_f32_16x16x4_f32) at <= 64 prefixes per decode; above, the three wide layer GEMMs on fp16 hi + lo pairs (three v_mfma_f32_16x16x32_f16 per product, fp32 accumulation; same ids on every test); greedy ids through an fp16 filter + exact fp32 re-evaluation"},
-                       "global_batch": BATCH * world, "parallelism": "dp%d (image shards, ids all-gather)" % world, "batches_in_flight_per_gpu": P, "batches_per_vit_launch": VB, "concurrent_decodes": DS if args.mode == "group" else 1,
-                       "pipelining": "none" if P == 1 else ("one decode per %d batches (up to %d decodes in flight, one decoder clone and stream each), overlapped with the next batches' ViT (one launch per %d batches) on %d stream(s)" % (P, DS, VB, S)
-                                                           if args.mode == "group" else "%d forwards on %d streams" % (P, P))},
             "roofline": roof,
             "roofline_in_pipeline": roof_pipe,
             "roofline_sync": roof_sync,
@@ -665,7 +686,7 @@ def main():
                      "note": "one forward at a time (batches_in_flight = 1), the reference eval scripts' call pattern"},
             "stages": stages,
             "preprocess": prep,
-        }
+        })
         if not args.no_configs and world == 1:           # BASELINE configs 3 / 4 / 5, per-GPU shards (N = 1 only: keeps an N-rank run inside the driver's budget)
             if pipe is not None and big_launch is None:
                 pipe.close()

@@ -9,6 +9,7 @@ run() {
   local envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done
   shift
+  set -- --full "$@"       # the fields read below are --full records
   env "${envs[@]}" timeout -k 10 280 python3 bench.py --no-cpu-baseline --no-configs "$@" 2> gpurun_out/sweep_err.log | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
