@@ -77,7 +77,10 @@ typedef struct {
    * position grid).  1: the OpenAI-CLIP ViT the reference loads through timm with QuickGELU for its "DeCap original"
    * configurations (P/src/model.py:358-392, 786-796; configs/decap_B16*.k.yaml, decap_B32.k.yaml): patch 16 / 32, no
    * registers, norm_pre after the position add, no LayerScale, x * sigmoid(1.702 x), final norm on every token and the
-   * bias-free head (embed_dim -> vit_out_dim) applied to every token; no qkv hook (has_attention = False, :864-865). */
+   * bias-free head (embed_dim -> vit_out_dim) applied to every token; no qkv hook (has_attention = False, :864-865).
+   * 2: AlphaCLIP's ViT (P/src/alphaclip/alpha_clip/model.py:351-380): arch 1 with a fourth, alpha input channel -- conv1(x) +
+   * conv1_alpha(alpha) before the position add (weight key patch_embed.alpha.weight [D,1,p,p]); pio_vit_forward is the all-ones
+   * alpha, pio_vit_forward_regions takes a mask per sequence. */
   int32_t vit_arch;
   int32_t vit_out_dim;        /* width of the tokens pio_vit_forward returns: 0 = embed_dim; 512 for the CLIP ViT-B head */
 } pio_config;
@@ -134,6 +137,27 @@ int pio_set_memory_bank_device(pio_handle h, const float* dev_bank, int64_t rows
  *    qkv_last_dev   [B,T,3D]  may be NULL */
 int pio_vit_forward(pio_handle h, const float* imgs_dev, int32_t B, float* tokens_dev, float* qkv_last_dev,
                     pio_stream stream);
+
+/* -- AlphaCLIP (vit_arch 2): one tower pass per region, the alpha mask as the fourth input channel
+ *    (forward_alphaclip_with_regions, P/src/model.py:1060-1354).  All pointers DEVICE.
+ *    imgs_dev           [B,3,crop,crop] fp32, the call's images
+ *    img_of_region_dev  [R] int32: sequence r reads image img_of_region[r] (NULL: image r)
+ *    masks_dev          [R,crop,crop] u8, nonzero = 1 (NULL: all ones, = pio_vit_forward)
+ *    tokens_dev         [R,T,vit_out_dim] as pio_vit_forward writes them;  1 <= R <= max_batch. */
+int pio_vit_forward_regions(pio_handle h, const float* imgs_dev, const int32_t* img_of_region_dev, const uint8_t* masks_dev, int32_t R,
+                            float* tokens_dev, pio_stream stream);
+
+/* -- AlphaCLIP region masks (P/src/alphaclip/alpha_mask_utils.py): region r = the union of its boxes and trace points on a
+ *    grid x grid raster, out masks_dev [R,grid,grid] u8 (0 / 1).  All pointers DEVICE.
+ *    boxes_dev  [nb,4] float32 x, y, w, h; region r owns boxes [box_off[r], box_off[r+1]) (box_off_dev [R+1] int32).  Box rule of
+ *               bbox_to_alpha_mask: end = x + w in float32, start and end floor-divided (torch's float //) by `divisor`, start
+ *               clamped to [0, grid-1], end to [0, grid], end EXCLUSIVE, empty unless end > start on both axes.
+ *    pts_dev    [np,2] float64 x, y; region r owns points [pt_off[r], pt_off[r+1]) (pt_off_dev [R+1] int32).  Point rule of
+ *               map_traces_to_grid (P/src/bbox_utils.py:158-168), made binary.
+ *    The tower's mask: grid = crop_dim, divisor 1; the patch average's: grid = crop_dim / patch_size, divisor patch_size.
+ *    boxes_dev / pts_dev may be NULL when the table holds none. */
+int pio_region_masks(pio_handle h, const float* boxes_dev, const int32_t* box_off_dev, const double* pts_dev, const int32_t* pt_off_dev,
+                     int32_t R, int32_t grid, float divisor, uint8_t* masks_dev, pio_stream stream);
 
 /* -- a4 + a5: CLS-row attention read-out and the two attention-weighted means
  *    (process_self_attention, P/src/dino_extraction.py:24-34; P/src/model.py:867-872).
@@ -425,6 +449,10 @@ int pio_test_attention(int32_t kind, int32_t operand, const void* q, const void*
  * t >= T of every Tp-row image dropped ([M / Tp * T][D]) */
 int pio_test_layernorm(int32_t operand, const float* x, const float* w, const float* b, float eps, int32_t M, int32_t D, void* out16,
                        float* out32, int32_t T, int32_t Tp, pio_stream stream);
+/* AlphaCLIP's four-channel patch rows (pio_vit_forward_regions' im2col): imgs [B][3][S][S] fp32, img_of_region [R] int32 (NULL: r),
+ * masks [R][S][S] u8 (NULL: ones) -> out [R * (S/p)^2][Kpad] in operand type 0 fp16, 1 bf16, 2 fp32; columns >= 4 p^2 not written. */
+int pio_test_im2col_alpha(int32_t operand, const float* imgs, const int32_t* img_of_region, const uint8_t* masks, int32_t R, int32_t S,
+                          int32_t p, int32_t Kpad, void* out, pio_stream stream);
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,8 @@ SIGNATURES = {
     "pio_set_memory_bank": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, POINTER(c_int64)]),
     "pio_set_memory_bank_device": (c_int32, [c_void_p, c_void_p, c_int64, c_int32]),
     "pio_vit_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "pio_vit_forward_regions": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "pio_region_masks": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p]),
     "pio_cls_attention": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
     "pio_trace_grids": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
@@ -129,6 +131,7 @@ SIGNATURES = {
                                      c_int32, c_int32, c_float, c_void_p, c_void_p]),
     "pio_test_layernorm": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                      c_int32, c_void_p]),
+    "pio_test_im2col_alpha": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

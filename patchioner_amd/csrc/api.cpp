@@ -84,6 +84,26 @@ struct GraphKey {
 
 }  // namespace
 
+// alpha.hip's launchers.  The library references them strongly: without alpha.hip its load fails (build() loads it with every
+// symbol bound).  Only the host-only AddressSanitizer build of this file alone (tests/hipstub, whose stub launchers predate these)
+// references them weakly; there the AlphaCLIP entry points report PIO_ERR_NOT_READY.
+#if defined(__SANITIZE_ADDRESS__)
+#define PIO_ALPHA_HOST_ONLY 1
+#elif defined(__has_feature)
+#if __has_feature(address_sanitizer)
+#define PIO_ALPHA_HOST_ONLY 1
+#endif
+#endif
+#ifdef PIO_ALPHA_HOST_ONLY
+namespace pio {
+hipError_t launch_im2col_alpha(int, const float*, const int32_t*, const uint8_t*, int, int, int, int, int, void*, hipStream_t) __attribute__((weak));
+hipError_t launch_region_masks(const float*, const int32_t*, const double*, const int32_t*, int, int, float, uint8_t*, hipStream_t) __attribute__((weak));
+}  // namespace pio
+#define PIO_ALPHA_LINKED (&launch_im2col_alpha != nullptr && &launch_region_masks != nullptr)
+#else
+#define PIO_ALPHA_LINKED true
+#endif
+
 struct pio_context {
   pio_config cfg;
   int n = 0, n2 = 0, T = 0, Tp = 0, Tk = 0, G = 0, D = 0, Kpe = 0, Kpad = 0, H = 0;
@@ -260,9 +280,22 @@ int finalize_vit(pio_context* c) {
   const int D = c->D, depth = c->cfg.depth, p = c->cfg.patch_size, R = c->cfg.num_registers;
   const HostTensor* t;
   int rc;
-  const bool clip = c->cfg.vit_arch == 1;
+  const bool clip = c->cfg.vit_arch >= 1, alpha = c->cfg.vit_arch == 2;
   if ((rc = need(c, "patch_embed.proj.weight", {D, 3, p, p}, &t))) return rc;
-  if ((rc = upload_op(c, t->data.data(), D, c->Kpe, c->Kpad, &c->pe_w))) return rc;
+  // the patch-embed operand [D][Kpe]: conv1's rows, and with the alpha channel (AlphaCLIP) conv1_alpha's p^2 columns after them, so that
+  // conv1(x) + conv1_alpha(alpha) is ONE GEMM over the four-channel patch rows (alpha.hip, k_im2col_alpha).  A checkpoint without
+  // conv1_alpha gets zeros (alpha_clip/model.py:603-606)
+  std::vector<float> pe_rows((size_t)D * c->Kpe, 0.f);
+  {
+    const int k3 = 3 * p * p;
+    const HostTensor* ta = alpha ? find(c, "patch_embed.alpha.weight") : nullptr;
+    if (ta && ta->numel() != (int64_t)D * p * p) return fail(PIO_ERR_SHAPE, "weight 'patch_embed.alpha.weight' is not [D, 1, p, p]");
+    for (int r = 0; r < D; ++r) {
+      memcpy(&pe_rows[(size_t)r * c->Kpe], &t->data[(size_t)r * k3], (size_t)k3 * 4);
+      if (ta) memcpy(&pe_rows[(size_t)r * c->Kpe + k3], &ta->data[(size_t)r * p * p], (size_t)p * p * 4);
+    }
+  }
+  if ((rc = upload_op(c, pe_rows.data(), D, c->Kpe, c->Kpad, &c->pe_w))) return rc;
   if (clip && !find(c, "patch_embed.proj.bias")) {          // CLIP's conv1 has no bias (timm: patch_embed.proj.bias absent)
     const std::vector<float> zeros(D, 0.f);
     if ((rc = upload_f32(c, zeros.data(), D, &c->pe_b))) return rc;
@@ -306,7 +339,7 @@ int finalize_vit(pio_context* c) {
       if ((rc = c->dmalloc(&c->tok_tmp, (size_t)c->cfg.max_batch * c->T * D, true))) return rc;
     }
   } else if (c->Dout != D) {
-    return fail(PIO_ERR_INVALID_ARG, "vit_out_dim != embed_dim needs vit_arch 1");
+    return fail(PIO_ERR_INVALID_ARG, "vit_out_dim != embed_dim needs vit_arch 1 or 2");
   }
   c->vl.resize(depth);
   for (int l = 0; l < depth; ++l) {
@@ -358,9 +391,8 @@ int finalize_vit(pio_context* c) {
     }
   }
   if (c->vit_f32) {
-    if ((rc = need(c, "patch_embed.proj.weight", {D, 3, p, p}, &t))) return rc;
     std::vector<float> pw((size_t)D * c->Kpad, 0.f);
-    for (int r = 0; r < D; ++r) memcpy(&pw[(size_t)r * c->Kpad], &t->data[(size_t)r * c->Kpe], (size_t)c->Kpe * 4);
+    for (int r = 0; r < D; ++r) memcpy(&pw[(size_t)r * c->Kpad], &pe_rows[(size_t)r * c->Kpe], (size_t)c->Kpe * 4);
     if ((rc = upload_f32(c, pw.data(), pw.size(), &c->pe_w32))) return rc;
     const size_t Bm = c->cfg.max_batch, Mm = Bm * c->Tp;
     if ((rc = c->dmalloc(&c->f_ape, Bm * c->n2 * c->Kpad, true))) return rc;
@@ -616,7 +648,7 @@ bool is_ignorable_key(const std::string& k) {
 
 bool is_known_key(const std::string& k) {
   static const char* exact[] = {"cls_token", "pos_embed", "register_tokens", "patch_embed.proj.weight",
-                                "patch_embed.proj.bias", "norm.weight", "norm.bias", "norm_pre.weight", "norm_pre.bias", "head.weight", "talk2dino.A_pinv",
+                                "patch_embed.proj.bias", "patch_embed.alpha.weight", "norm.weight", "norm.bias", "norm_pre.weight", "norm_pre.bias", "head.weight", "talk2dino.A_pinv",
                                 "talk2dino.b"};
   for (auto e : exact) if (k == e) return true;
   return k.rfind("blocks.", 0) == 0 || k.rfind("decoder.transformer.", 0) == 0 || k.rfind("clip_project.model.0.", 0) == 0 ||
@@ -723,11 +755,12 @@ int pio_create(const pio_config* cfg, pio_handle* out) {
     return fail(PIO_ERR_INVALID_ARG, "pio_create: capacities out of range (prefixes <= 256, decoder positions <= 256)");
   if (cfg->readout_heads != 16 && cfg->readout_heads * 64 != cfg->embed_dim)
     return fail(PIO_ERR_INVALID_ARG, "pio_create: readout_heads must be 16, or embed_dim / 64 (ViT-S: 6)");
-  if (cfg->vit_arch != 0 && cfg->vit_arch != 1) return fail(PIO_ERR_INVALID_ARG, "pio_create: vit_arch must be 0 (DINOv2) or 1 (OpenAI-CLIP ViT)");
-  if (cfg->vit_arch == 1 && cfg->num_registers != 0)
+  if (cfg->vit_arch < 0 || cfg->vit_arch > 2)
+    return fail(PIO_ERR_INVALID_ARG, "pio_create: vit_arch must be 0 (DINOv2), 1 (OpenAI-CLIP ViT) or 2 (AlphaCLIP ViT)");
+  if (cfg->vit_arch >= 1 && cfg->num_registers != 0)
     return fail(PIO_ERR_INVALID_ARG, "pio_create: the CLIP ViT has no registers");
   if (cfg->vit_out_dim < 0 || (cfg->vit_out_dim > 0 && cfg->vit_out_dim % 32 != 0) || (cfg->vit_arch == 0 && cfg->vit_out_dim != 0 && cfg->vit_out_dim != cfg->embed_dim))
-    return fail(PIO_ERR_INVALID_ARG, "pio_create: vit_out_dim must be 0, or a multiple of 32 with vit_arch 1");
+    return fail(PIO_ERR_INVALID_ARG, "pio_create: vit_out_dim must be 0, or a multiple of 32 with vit_arch 1 or 2");
   int ndev = 0;
   HIP_OK(hipGetDeviceCount(&ndev));
   if (cfg->device < 0 || cfg->device >= ndev) return fail(PIO_ERR_INVALID_ARG, "pio_create: no such HIP device");
@@ -742,8 +775,10 @@ int pio_create(const pio_config* cfg, pio_handle* out) {
   c->T = c->G + c->n2;
   c->Tp = round_up(c->T, 8);
   c->Tk = round_up(c->T, 64);
-  c->Kpe = 3 * cfg->patch_size * cfg->patch_size;
-  c->Kpad = round_up(c->Kpe, 64);
+  c->Kpe = (cfg->vit_arch == 2 ? 4 : 3) * cfg->patch_size * cfg->patch_size;     // AlphaCLIP: conv1 | conv1_alpha
+  // AlphaCLIP: every patch-embed GEMM kernel takes K in steps of 128 (two 64-wide K-tiles); 4 p^2 is 1024 at p = 16 and 4096 at p = 32,
+  // but 784 at p = 14 (ViT-L/14), which round_up(., 64) would leave at 832, a K no kernel routes
+  c->Kpad = round_up(c->Kpe, cfg->vit_arch == 2 ? 128 : 64);
   c->op = cfg->vit_operand_type == 1 ? OP_BF16 : OP_F16;
   c->vit_f32 = cfg->vit_operand_type == 2;
   c->Dout = cfg->vit_out_dim > 0 ? cfg->vit_out_dim : cfg->embed_dim;
@@ -970,7 +1005,7 @@ static int run_vit_block_f32(pio_handle c, int l, int B, float* qkv_last, const 
   HIP_OK(launch_resid_ls_f32(c->x, c->f_xn, L.ls1, (size_t)M * D, D, s));
   HIP_OK(launch_layernorm_f32(c->x, L.n2w, L.n2b, eps, M, D, c->f_xn, s));
   HIP_OK(launch_sgemm_tn(c->f_xn, D, W.fc1w, D, L.fc1b, 1.f, c->f_h, 4 * D, M, 4 * D, D, 0, 0, s));
-  HIP_OK(launch_gelu_f32(c->f_h, (size_t)M * 4 * D, c->cfg.vit_arch == 1 ? 1 : 0, s));
+  HIP_OK(launch_gelu_f32(c->f_h, (size_t)M * 4 * D, c->cfg.vit_arch >= 1 ? 1 : 0, s));
   HIP_OK(launch_sgemm_tn(c->f_h, 4 * D, W.fc2w, 4 * D, L.fc2b, 1.f, c->f_xn, D, M, D, 4 * D, 0, 0, s));
   HIP_OK(launch_resid_ls_f32(c->x, c->f_xn, L.ls2, (size_t)M * D, D, s));
   return PIO_OK;
@@ -1013,7 +1048,7 @@ static int run_vit_block(pio_handle c, const VitLayerDev& L, int B, const GemmAr
   {
     GemmArgs a = g;
     a.A = c->xn; a.lda = D; a.W = L.fc1w; a.bias = L.fc1b; a.out16 = c->hbuf; a.M = M; a.N = 4 * D; a.K = D;
-    a.act = c->cfg.vit_arch == 1 ? 1 : 0;
+    a.act = c->cfg.vit_arch >= 1 ? 1 : 0;
     a.pf = L.fc2w; a.pf_bytes = 4 * D * D * 2;
     PROF(c, PIO_PROF_VIT_GEMM, 2.0 * Malg * 4.0 * D * D, 0, s, launch_vit_gemm(c->op, EPI_GELU, a, s));
   }
@@ -1026,20 +1061,22 @@ static int run_vit_block(pio_handle c, const VitLayerDev& L, int B, const GemmAr
   return PIO_OK;
 }
 
-int pio_vit_forward(pio_handle c, const float* imgs, int32_t B, float* tokens, float* qkv_last, pio_stream stream) {
-  if (!c || !imgs || !tokens) return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward: null argument");
-  if (c->cfg.vit_arch == 1 && qkv_last) return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward: the CLIP ViT has no qkv capture (no hook in the reference, P/src/model.py:586-590 is DINOv2 only)");
-  if (!c->has_vit) return fail(PIO_ERR_NOT_READY, "pio_vit_forward: backbone weights not loaded");
-  if (B < 1 || B > c->cfg.max_batch) return fail(PIO_ERR_CAPACITY, "pio_vit_forward: batch above max_batch");
-  HIP_OK(hipSetDevice(c->cfg.device));
-  hipStream_t s = (hipStream_t)stream;
+// The forward of B sequences.  AlphaCLIP (vit_arch 2): sequence r is image img_of_region[r] (null: r) with the alpha mask masks[r]
+// (u8 [B][S][S]; null: ones); the other families read image r and take no mask.
+static int vit_forward_impl(pio_handle c, const float* imgs, int32_t B, const int32_t* img_of_region, const uint8_t* masks, float* tokens,
+                            float* qkv_last, hipStream_t s) {
   const int D = c->D, M = B * c->Tp;
+  const bool alpha = c->cfg.vit_arch == 2;
+  if (alpha && !PIO_ALPHA_LINKED) return fail(PIO_ERR_NOT_READY, "vit forward: the alpha-channel kernels are not linked");
   if (c->vit_f32) {
-    HIP_OK(launch_im2col_f32(imgs, B, c->cfg.crop_dim, c->cfg.patch_size, c->n, c->Kpad, c->f_ape, s));
+    if (alpha)
+      HIP_OK(launch_im2col_alpha(2, imgs, img_of_region, masks, B, c->cfg.crop_dim, c->cfg.patch_size, c->n, c->Kpad, c->f_ape, s));
+    else
+      HIP_OK(launch_im2col_f32(imgs, B, c->cfg.crop_dim, c->cfg.patch_size, c->n, c->Kpad, c->f_ape, s));
     HIP_OK(launch_token_init(c->x, c->cls, c->pos, c->reg, B, c->cfg.num_registers, c->T, c->Tp, D, s));
     HIP_OK(launch_sgemm_tn(c->f_ape, c->Kpad, c->pe_w32, c->Kpad, c->pe_b, 1.f, c->f_emb, D, B * c->n2, D, c->Kpad, 0, 0, s));
     HIP_OK(launch_embed_scatter_f32(c->f_emb, c->pos, B, c->n2, c->Tp, c->G, D, c->x, s));
-    if (c->cfg.vit_arch == 1) HIP_OK(launch_layernorm_f32(c->x, c->npre_w, c->npre_b, c->cfg.vit_ln_eps, M, D, c->x, s));
+    if (c->cfg.vit_arch >= 1) HIP_OK(launch_layernorm_f32(c->x, c->npre_w, c->npre_b, c->cfg.vit_ln_eps, M, D, c->x, s));
     for (int l = 0; l < c->cfg.depth; ++l) {
       const int rc = run_vit_block_f32(c, l, B, (l == c->cfg.depth - 1) ? qkv_last : nullptr, nullptr, s);
       if (rc != PIO_OK) return rc;
@@ -1052,7 +1089,11 @@ int pio_vit_forward(pio_handle c, const float* imgs, int32_t B, float* tokens, f
     }
     return PIO_OK;
   }
-  HIP_OK(launch_im2col(c->op, imgs, B, c->cfg.crop_dim, c->cfg.patch_size, c->n, c->Kpad, c->ape, s));
+  if (alpha)
+    HIP_OK(launch_im2col_alpha(c->op == OP_F16 ? 0 : 1, imgs, img_of_region, masks, B, c->cfg.crop_dim, c->cfg.patch_size, c->n, c->Kpad,
+                               c->ape, s));
+  else
+    HIP_OK(launch_im2col(c->op, imgs, B, c->cfg.crop_dim, c->cfg.patch_size, c->n, c->Kpad, c->ape, s));
   HIP_OK(launch_token_init(c->x, c->cls, c->pos, c->reg, B, c->cfg.num_registers, c->T, c->Tp, D, s));
   GemmArgs g;
   memset(&g, 0, sizeof(g));
@@ -1063,7 +1104,7 @@ int pio_vit_forward(pio_handle c, const float* imgs, int32_t B, float* tokens, f
     a.A = c->ape; a.lda = c->Kpad; a.W = c->pe_w; a.bias = c->pe_b; a.M = B * c->n2; a.N = D; a.K = c->Kpad;
     PROF(c, PIO_PROF_VIT_GEMM, 2.0 * B * c->n2 * (double)D * c->Kpe, 0, s, launch_vit_gemm(c->op, EPI_PATCH_EMBED, a, s));
   }
-  if (c->cfg.vit_arch == 1)     // CLIP: norm_pre on the position-added tokens, in place (fp32; every row is read whole before it is written)
+  if (c->cfg.vit_arch >= 1)     // CLIP: norm_pre on the position-added tokens, in place (fp32; every row is read whole before it is written)
     HIP_OK(launch_layernorm(c->op, c->x, c->npre_w, c->npre_b, c->cfg.vit_ln_eps, M, D, nullptr, c->x, c->Tp, c->Tp, s));
   VitAttnArgs at;
   at.q = c->q; at.k = c->k; at.vT = c->vT; at.out = c->ao; at.B = B; at.H = c->H; at.T = c->T; at.Tp = c->Tp;
@@ -1083,11 +1124,40 @@ int pio_vit_forward(pio_handle c, const float* imgs, int32_t B, float* tokens, f
   return PIO_OK;
 }
 
+int pio_vit_forward(pio_handle c, const float* imgs, int32_t B, float* tokens, float* qkv_last, pio_stream stream) {
+  if (!c || !imgs || !tokens) return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward: null argument");
+  if (c->cfg.vit_arch >= 1 && qkv_last) return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward: the CLIP ViT has no qkv capture (no hook in the reference, P/src/model.py:586-590 is DINOv2 only)");
+  if (!c->has_vit) return fail(PIO_ERR_NOT_READY, "pio_vit_forward: backbone weights not loaded");
+  if (B < 1 || B > c->cfg.max_batch) return fail(PIO_ERR_CAPACITY, "pio_vit_forward: batch above max_batch");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  return vit_forward_impl(c, imgs, B, nullptr, nullptr, tokens, qkv_last, (hipStream_t)stream);
+}
+
+int pio_vit_forward_regions(pio_handle c, const float* imgs, const int32_t* img_of_region, const uint8_t* masks, int32_t R, float* tokens,
+                            pio_stream stream) {
+  if (!c || !imgs || !tokens) return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward_regions: null argument");
+  if (c->cfg.vit_arch != 2) return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward_regions: an alpha-channel tower only (vit_arch 2, AlphaCLIP)");
+  if (!c->has_vit) return fail(PIO_ERR_NOT_READY, "pio_vit_forward_regions: backbone weights not loaded");
+  if (R < 1 || R > c->cfg.max_batch) return fail(PIO_ERR_CAPACITY, "pio_vit_forward_regions: regions outside 1..max_batch");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  return vit_forward_impl(c, imgs, R, img_of_region, masks, tokens, nullptr, (hipStream_t)stream);
+}
+
+int pio_region_masks(pio_handle c, const float* boxes, const int32_t* box_off, const double* pts, const int32_t* pt_off, int32_t R,
+                     int32_t grid, float divisor, uint8_t* masks, pio_stream stream) {
+  if (!c || !box_off || !pt_off || !masks) return fail(PIO_ERR_INVALID_ARG, "pio_region_masks: null argument");
+  if (R < 1 || grid < 1 || grid > 4096 || !(divisor > 0.f)) return fail(PIO_ERR_INVALID_ARG, "pio_region_masks: R >= 1, 1 <= grid <= 4096, divisor > 0");
+  if (!PIO_ALPHA_LINKED) return fail(PIO_ERR_NOT_READY, "pio_region_masks: the alpha-channel kernels are not linked");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  HIP_OK(launch_region_masks(boxes, box_off, pts, pt_off, R, grid, divisor, masks, (hipStream_t)stream));
+  return PIO_OK;
+}
+
 int pio_bbox_double_dino(pio_handle c, const float* tokens, const int32_t* slices, int32_t B, int32_t NB, int32_t use_cls,
                          int32_t return_type, float* out, pio_stream stream) {
   if (!c || !tokens || !slices || !out) return fail(PIO_ERR_INVALID_ARG, "pio_bbox_double_dino: null argument");
   if (!c->has_vit) return fail(PIO_ERR_NOT_READY, "pio_bbox_double_dino: backbone weights not loaded");
-  if (c->cfg.vit_arch == 1) return fail(PIO_ERR_INVALID_ARG, "pio_bbox_double_dino: DINOv2 backbones only (P/src/bbox_utils.py:300-403 re-runs a DINOv2 block)");
+  if (c->cfg.vit_arch >= 1) return fail(PIO_ERR_INVALID_ARG, "pio_bbox_double_dino: DINOv2 backbones only (P/src/bbox_utils.py:300-403 re-runs a DINOv2 block)");
   if (B < 1 || NB < 1) return fail(PIO_ERR_INVALID_ARG, "pio_bbox_double_dino: empty batch");
   if (return_type < 0 || return_type > 1) return fail(PIO_ERR_INVALID_ARG, "pio_bbox_double_dino: return_type 0 (cls) or 1 (avg)");
   if (return_type == 0 && !use_cls) return fail(PIO_ERR_INVALID_ARG, "pio_bbox_double_dino: return_type cls needs use_cls");
@@ -1121,7 +1191,7 @@ int pio_cls_attention(pio_handle c, const float* qkv_last, const float* tokens, 
                       float* head_maps, float* avg_token, float* disentangled, pio_stream stream) {
   if (!c || !qkv_last || !self_attn) return fail(PIO_ERR_INVALID_ARG, "pio_cls_attention: null argument");
   if (!c->has_vit) return fail(PIO_ERR_NOT_READY, "pio_cls_attention: backbone not loaded");
-  if (c->cfg.vit_arch == 1) return fail(PIO_ERR_INVALID_ARG, "pio_cls_attention: the CLIP ViT exposes no qkv hook (has_attention = False, P/src/model.py:864-865)");
+  if (c->cfg.vit_arch >= 1) return fail(PIO_ERR_INVALID_ARG, "pio_cls_attention: the CLIP ViT exposes no qkv hook (has_attention = False, P/src/model.py:864-865)");
   if (B < 1 || B > c->cfg.max_batch) return fail(PIO_ERR_CAPACITY, "pio_cls_attention: batch above max_batch");
   if ((avg_token || disentangled) && !tokens) return fail(PIO_ERR_INVALID_ARG, "pio_cls_attention: tokens required");
   HIP_OK(hipSetDevice(c->cfg.device));
@@ -1724,8 +1794,8 @@ int pio_preprocess(pio_handle c, const void* pixels, const int64_t* offsets, con
     // ImageNet statistics for DINOv2 (P/src/model.py:351), OpenAI-CLIP's for the CLIP ViT (:381-382)
     static const float mean_in[3] = {0.485f, 0.456f, 0.406f}, std_in[3] = {0.229f, 0.224f, 0.225f};
     static const float mean_cl[3] = {0.48145466f, 0.4578275f, 0.40821073f}, std_cl[3] = {0.26862954f, 0.26130258f, 0.27577711f};
-    const float* mean = c->cfg.vit_arch == 1 ? mean_cl : mean_in;
-    const float* stdv = c->cfg.vit_arch == 1 ? std_cl : std_in;
+    const float* mean = c->cfg.vit_arch >= 1 ? mean_cl : mean_in;
+    const float* stdv = c->cfg.vit_arch >= 1 ? std_cl : std_in;
     std::vector<float> lut(768);
     for (int ch = 0; ch < 3; ++ch)
       for (int v = 0; v < 256; ++v) {

@@ -120,6 +120,15 @@ hipError_t launch_text_pool(const float* x, const int32_t* ids, int N, int L, in
 // imgs [B][3][S][S] fp32 -> patch rows [B*n2][Kpad] (k = c*p*p + py*p + px; columns >= 3*p*p stay zero)
 hipError_t launch_im2col(OperandType t, const float* imgs, int B, int S, int p, int n, int Kpad, void* out,
                          hipStream_t s);
+// ---- alpha.hip: AlphaCLIP's region masks and four-channel patch rows
+// masks out [R][grid][grid] u8: region r = union of boxes [box_off[r], box_off[r+1]) (xywh float32, floor-divided by `divisor`, end
+// exclusive) and of the trace points [pt_off[r], pt_off[r+1]) (x, y float64 in [0, 1]); boxes / pts may be null when they hold none
+hipError_t launch_region_masks(const float* boxes, const int32_t* box_off, const double* pts, const int32_t* pt_off, int R, int grid,
+                               float divisor, uint8_t* out, hipStream_t s);
+// rows [R*n2][Kpad] (type 0 fp16, 1 bf16, 2 fp32): columns [0, 3p^2) = image img_of_region[r] (null: r) as launch_im2col,
+// [3p^2, 4p^2) = masks[r] (u8 [R][S][S], nonzero = 1; null: all ones); columns >= 4p^2 are not written
+hipError_t launch_im2col_alpha(int type, const float* imgs, const int32_t* img_of_region, const uint8_t* masks, int R, int S, int p,
+                               int n, int Kpad, void* out, hipStream_t s);
 // x[b][0] = cls + pos[0]; x[b][1..R] = registers; x[b][T..Tp-1] = 0
 // double-DINO boxes (P/src/bbox_utils.py:300-403): sequence s = (image, box) -> x[s] = [cls | registers | region patches]
 // (final tokens; `slices` [Ns][4] = python-normalised ys, ye, xs, xe), zero rows up to Tp; lens[s] = its token count

@@ -131,4 +131,15 @@ int pio_test_layernorm(int32_t operand, const float* x, const float* w, const fl
   return PIO_OK;
 }
 
+int pio_test_im2col_alpha(int32_t operand, const float* imgs, const int32_t* img_of_region, const uint8_t* masks, int32_t R, int32_t S,
+                          int32_t p, int32_t Kpad, void* out, pio_stream stream) {
+  if (operand < 0 || operand > 2) return fail(PIO_ERR_INVALID_ARG, "pio_test_im2col_alpha: operand 0 (fp16), 1 (bf16) or 2 (fp32)");
+  if (!imgs || !out || R < 1 || p < 1 || S < p || S % p != 0 || Kpad < 4 * p * p)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_im2col_alpha: imgs, out, R >= 1, S a multiple of p, Kpad >= 4 p^2");
+  const hipError_t e = launch_im2col_alpha(operand, imgs, img_of_region, masks, R, S, p, S / p, Kpad, out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_im2col_alpha: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_im2col_alpha: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
 }  // extern "C"

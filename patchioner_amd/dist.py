@@ -123,6 +123,8 @@ def _all_ranks_ok(ok: bool, what: str, group=None) -> None:
 def sharded_trace_captions(model, imgs: torch.Tensor, traces: Sequence, detokenize, group=None, **fwd) -> List[str]:
     """Caption a global batch: every rank receives the same (imgs, traces), processes its contiguous shard
     with `model(...)` and all ranks return the captions of the whole batch in the original order."""
+    if getattr(model, "backbone_type", None) == 'AlphaClip':
+        raise NotImplementedError("sharded_trace_captions: AlphaCLIP region captions are not sharded; call forward() on each rank's images")
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     s, e = shard_bounds(imgs.shape[0], world, rank)
@@ -145,6 +147,8 @@ def sharded_box_captions(model, imgs: torch.Tensor, bboxes: torch.Tensor, detoke
     boxes of its contiguous IMAGE shard with ``model(..., bboxes=...)`` and all ranks return the whole batch's captions as
     [B][NB], in the original order.  One exchange: the ragged all-gather of the shard's [n_local * NB, steps] token ids.
     The caller's ``bboxes`` tensor is floor-divided by the patch size in place, as the reference's forward does."""
+    if getattr(model, "backbone_type", None) == 'AlphaClip':
+        raise NotImplementedError("sharded_box_captions: AlphaCLIP region captions are not sharded; call forward() on each rank's images")
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     B, NB = bboxes.shape[0], bboxes.shape[1]

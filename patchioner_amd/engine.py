@@ -39,7 +39,7 @@ class Engine:
             dec_embd=dec_embd, dec_vocab=dec_vocab, dec_positions=dec_positions, prefix_size=prefix_size,
             dec_ln_eps=1e-5, max_batch=max_batch, max_prefixes=max_prefixes, max_steps=max_steps,
             vit_operand_type={"fp16": 0, "bf16": 1, "fp32": 2}[vit_dtype], device=device_index,
-            vit_arch={"dinov2": 0, "clip": 1}[vit_arch], vit_out_dim=vit_out_dim)
+            vit_arch={"dinov2": 0, "clip": 1, "alphaclip": 2}[vit_arch], vit_out_dim=vit_out_dim)
         self.cfg = cfg
         h = ctypes.c_void_p()
         check(self.lib.pio_create(ctypes.byref(cfg), ctypes.byref(h)))
@@ -149,6 +149,48 @@ class Engine:
             check(self.lib.pio_vit_forward(self.h, ptr(imgs[s:e]), e - s, ptr(tokens[s:e]),
                                            ptr(qkv[s:e]) if want_qkv else None, _stream()))
         return tokens, qkv
+
+    def region_masks(self, regions: Sequence[Tuple[Sequence[Sequence[float]], Sequence[Tuple[float, float]]]], grid: int,
+                     divisor: int) -> torch.Tensor:
+        """AlphaCLIP region masks on the device (pio_region_masks): ``regions`` = one (boxes [[x, y, w, h], ...], points [(x, y), ...])
+        pair per region, the mask being their union -> uint8 [R, grid, grid] (0 / 1).  One table upload, one launch."""
+        R = len(regions)
+        boxes = np.array([b for bx, _ in regions for b in bx], dtype=np.float32).reshape(-1, 4)
+        pts = np.array([q for _, pt in regions for q in pt], dtype=np.float64).reshape(-1, 2)
+        if not np.isfinite(boxes).all():        # int() of a NaN / inf box end fails in bbox_to_alpha_mask; such trace points are skipped
+            raise ValueError("cannot convert float NaN / inf box coordinates to integer")
+        box_off = np.zeros(R + 1, dtype=np.int32)
+        pt_off = np.zeros(R + 1, dtype=np.int32)
+        np.cumsum([len(bx) for bx, _ in regions], out=box_off[1:])
+        np.cumsum([len(pt) for _, pt in regions], out=pt_off[1:])
+        bd = torch.from_numpy(boxes).to(self.device) if len(boxes) else None
+        pd = torch.from_numpy(pts).to(self.device) if len(pts) else None
+        bo, po = torch.from_numpy(box_off).to(self.device), torch.from_numpy(pt_off).to(self.device)
+        out = torch.empty(R, grid, grid, device=self.device, dtype=torch.uint8)
+        check(self.lib.pio_region_masks(self.h, ptr(bd), ptr(bo), ptr(pd), ptr(po), R, int(grid), float(divisor), ptr(out), _stream()))
+        return out
+
+    def vit_forward_regions(self, imgs: torch.Tensor, img_of_region: torch.Tensor, masks: Optional[torch.Tensor]) -> torch.Tensor:
+        """AlphaCLIP: one tower pass per region (pio_vit_forward_regions), region r on image img_of_region[r] with the alpha mask
+        masks[r] (uint8 [R, S, S]; None: ones) -> tokens [R, T, D], in launches of at most max_batch regions."""
+        imgs = self._dev(imgs)
+        crop = self.cfg.crop_dim
+        if tuple(imgs.shape[1:]) != (3, crop, crop):
+            raise ValueError("images must be [B,3,%d,%d], got %s" % (crop, crop, tuple(imgs.shape)))
+        idx = self._dev(img_of_region, torch.int32)
+        R = int(idx.shape[0])
+        if R and (int(idx.min()) < 0 or int(idx.max()) >= imgs.shape[0]):
+            raise IndexError("img_of_region outside the %d images of the call" % imgs.shape[0])
+        if masks is not None:
+            masks = masks.to(device=self.device, dtype=torch.uint8).contiguous()
+            if tuple(masks.shape) != (R, crop, crop):
+                raise ValueError("masks must be [R,%d,%d], got %s" % (crop, crop, tuple(masks.shape)))
+        tokens = torch.empty(R, self.T, self.D, device=self.device, dtype=torch.float32)
+        for s in range(0, R, self.max_batch):
+            e = min(R, s + self.max_batch)
+            check(self.lib.pio_vit_forward_regions(self.h, ptr(imgs), ptr(idx[s:e]), ptr(masks[s:e]) if masks is not None else None,
+                                                   e - s, ptr(tokens[s:e]), _stream()))
+        return tokens
 
     # ------------------------------------------------------------------ a4/a5 read-out
     def cls_attention(self, qkv: torch.Tensor, tokens: torch.Tensor, want_maps=False, want_avg=False,

@@ -39,8 +39,7 @@ from .engine import Engine
 from .preprocess import make_transforms
 from .tokenizer import ClipDetokenizer
 
-_OUT_OF_SCOPE = ("proxyclip_clipmodel", "regionclip_config", "invite_config", "denseclip_config",
-                 "alphaclip_config", "clipcap_config")
+_OUT_OF_SCOPE = ("proxyclip_clipmodel", "regionclip_config", "invite_config", "denseclip_config", "clipcap_config")
 
 
 def _load_state_dict(spec):
@@ -97,8 +96,7 @@ class Patchioner(nn.Module):
         super().__init__(**kwargs)
         given = dict(proxyclip_clipmodel=proxyclip_clipmodel,
                      regionclip_config=regionclip_config, invite_config=invite_config,
-                     denseclip_config=denseclip_config, alphaclip_config=alphaclip_config,
-                     clipcap_config=clipcap_config)
+                     denseclip_config=denseclip_config, clipcap_config=clipcap_config)
         for k in _OUT_OF_SCOPE:
             if given[k] is not None:
                 raise NotImplementedError("%s: backbone/head outside the MI355X hot-path scope (DINOv2 + DeCap/CapDec)" % k)
@@ -109,13 +107,36 @@ class Patchioner(nn.Module):
             raise TypeError("online_texts must be a list of str")
         if online_texts is not None and support_memory_size > 0 and len(online_texts) == 0:
             raise ValueError("online_texts is empty")
+        is_alpha = alphaclip_config is not None
+        alpha_sd = None
+        if is_alpha:
+            # P/src/model.py:515-545 (alphaclip_loader.load_alphaclip): AlphaCLIP's ViT, the OpenAI-CLIP tower with an alpha input
+            # channel.  Name, crop and weights are checked here, before anything touches the device.
+            alpha_name = alphaclip_config.get('name', None)
+            alpha_dv, _, alpha_heads, alpha_p, alpha_out, alpha_crop = W.alphaclip_arch(alpha_name)
+            if alphaclip_config.get('patch_size', alpha_p) != alpha_p:
+                raise ValueError("alphaclip_config patch_size %r: the %s tower's patches are %d pixels" % (alphaclip_config['patch_size'], alpha_name, alpha_p))
+            if crop_dim != alpha_crop:
+                # alpha_clip/model.py:372: the position table is never resampled, the add fails for any other crop
+                raise RuntimeError("The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 1: the %s "
+                                   "tower takes %d x %d crops" % ((crop_dim // alpha_p) ** 2 + 1, (alpha_crop // alpha_p) ** 2 + 1, alpha_name,
+                                                                   alpha_crop, alpha_crop))
+            alpha_sd = _load_state_dict(alphaclip_config.get('alpha_vision_checkpoint', None))
+            if alpha_sd is None:
+                if synthetic_seed is None:
+                    raise FileNotFoundError("alphaclip_config['alpha_vision_checkpoint'] is required (alpha_clip.load downloads the CLIP "
+                                            "weights, which needs network this target does not have), or synthetic_seed")
+                alpha_sd = W.synth_alphaclip_vit(synthetic_seed + 1, alpha_name)
+            alpha_sd = W.alphaclip_to_engine(alpha_sd)
         # P/src/model.py:339-392: 'dinov2' names load from torch.hub, 'openai' names are the timm OpenAI-CLIP towers of the
         # "DeCap original" configurations (configs/decap_B16*.k.yaml, decap_B32.k.yaml)
         is_clip = dino_model is not None and 'openai' in dino_model and 'dinov2' not in dino_model
-        if dino_model is None or 'dinotxt' in dino_model or not ('dinov2' in dino_model or is_clip):
+        if is_alpha:
+            pass
+        elif dino_model is None or 'dinotxt' in dino_model or not ('dinov2' in dino_model or is_clip):
             raise ValueError("Unsupported backbone %r: this build implements the DINOv2 ViT-S/B/L-14 family and the timm "
                              "OpenAI-CLIP ViTs (vit_base_patch16/32_clip_224.openai)" % (dino_model,))
-        if is_clip and resize_dim != crop_dim:
+        if is_clip and not is_alpha and resize_dim != crop_dim:
             # P/src/model.py:371 builds the tower with img_size=resize_dim: timm's PatchEmbed then asserts that every input is
             # resize_dim x resize_dim, while the transforms crop to crop_dim -- the reference's first forward fails; fail at once
             raise AssertionError("Input height (%d) doesn't match model (%d)." % (crop_dim, resize_dim))
@@ -147,8 +168,13 @@ class Patchioner(nn.Module):
         self.resize_dim = resize_dim
         self.crop_dim = crop_dim
         self.model_name = dino_model
-        self.num_global_tokens = 1 if "reg" not in dino_model else 5
-        if is_clip:
+        self.num_global_tokens = 1 if is_alpha or "reg" not in dino_model else 5
+        if is_alpha:
+            # the tower is alpha_dv wide; the reference's embed_dim is alphaclip_config['embed_dim'] (model.py:305-310), the head's width
+            depth, heads, patch_size, self.token_dim = 0, alpha_heads, alpha_p, alpha_out
+            self.embed_dim = alphaclip_config.get('embed_dim', alpha_out)
+            self.alphaclip_config = dict(alphaclip_config)
+        elif is_clip:
             # timm VisionTransformer with pre_norm, nn.LayerNorm (eps 1e-5), QuickGELU (model.py:363-371); the reference hands
             # img_size=resize_dim to timm, which resamples the checkpoint's position table for any size but 224 at load
             # (configs/decap_B16_resize.k.yaml: 592): pio_finalize_weights does the same from the table's own grid
@@ -161,24 +187,24 @@ class Patchioner(nn.Module):
             raise ValueError("crop_dim must be a multiple of %d (the reference's reshape fails otherwise)" % patch_size)
         self.num_patch_tokens = crop_dim // patch_size * crop_dim // patch_size
         self.num_tokens = self.num_global_tokens + self.num_patch_tokens
-        self.num_attn_heads = 16 if 'vits' not in dino_model else 6
+        self.num_attn_heads = 16 if is_alpha or 'vits' not in dino_model else 6
         self.scale = 0.125
         self.patch_size = patch_size
-        self.backbone_type = 'CLIP' if is_clip else 'DINO'            # model.py:650-651, :786
-        if is_clip:
+        self.backbone_type = 'AlphaClip' if is_alpha else ('CLIP' if is_clip else 'DINO')            # model.py:650-651, :786, :642-644
+        if is_clip or is_alpha:
             from .preprocess import CLIP_MEAN, CLIP_STD
             self.image_transforms, self.image_transforms_no_crop = make_transforms(resize_dim, crop_dim, CLIP_MEAN, CLIP_STD)
         else:
             self.image_transforms, self.image_transforms_no_crop = make_transforms(resize_dim, crop_dim)
 
-        vit_sd = _load_state_dict(dino_weights)
+        vit_sd = alpha_sd if is_alpha else _load_state_dict(dino_weights)
         if vit_sd is None:
             if synthetic_seed is None:
                 raise FileNotFoundError("dino_weights is required: torch.hub.load('facebookresearch/dinov2', ...) / "
                                         "timm.create_model(..., pretrained=True) need network, which this target does not have")
             vit_sd = W.synth_clip_vit(synthetic_seed + 1, dino_model) if is_clip else W.synth_dinov2(synthetic_seed + 1, dino_model)
         depth = 1 + max(int(k.split(".")[1]) for k in vit_sd if k.startswith("blocks."))
-        if attention_type != 'qkv' and not is_clip:
+        if attention_type != 'qkv' and not is_clip and not is_alpha:
             # the reference re-orders the last block's fused q|k|v rows (P/src/model.py:569-582)
             vit_sd = dict(vit_sd)
             D = self.embed_dim
@@ -217,13 +243,13 @@ class Patchioner(nn.Module):
             dec_kw = dict(dec_layers=n_layer, dec_heads=12, max_steps=256,
                           dec_vocab=int(viecap_sd["gpt.transformer.wte.weight"].shape[0]),
                           dec_positions=int(viecap_sd["gpt.transformer.wpe.weight"].shape[0]))
-        self.engine = Engine(embed_dim=self.embed_dim, depth=depth, num_heads=heads,
+        self.engine = Engine(embed_dim=alpha_dv if is_alpha else self.embed_dim, depth=depth, num_heads=heads,
                              num_registers=self.num_global_tokens - 1, crop_dim=crop_dim, patch_size=patch_size,
                              pretrain_grid=int(math.isqrt(vit_sd["pos_embed"].shape[1] - 1)), prefix_size=prefix_size,
                              max_batch=max_batch, max_prefixes=max_prefixes, vit_dtype=vit_dtype,
                              device_index=self._device.index, readout_heads=self.num_attn_heads, readout_scale=self.scale,
-                             vit_arch="clip" if is_clip else "dinov2", vit_out_dim=self.token_dim if is_clip else 0,
-                             vit_ln_eps=1e-5 if is_clip else 1e-6, **dec_kw)
+                             vit_arch="alphaclip" if is_alpha else ("clip" if is_clip else "dinov2"),
+                             vit_out_dim=self.token_dim if is_clip or is_alpha else 0, vit_ln_eps=1e-5 if is_clip or is_alpha else 1e-6, **dec_kw)
         self.engine.load_state_dict(vit_sd)
         if dec_sd is not None:                         # calculate_argmax_text without decoder weights: no decoder (model.py:165)
             self.engine.load_state_dict(dec_sd)        # strict=False like the reference (decap.py:214)
@@ -255,7 +281,7 @@ class Patchioner(nn.Module):
             else:
                 raise FileNotFoundError("support_memory_size > 0 needs `memory_bank` (path or tensor): building the "
                                         "bank (CLIP text tower + datasets) is offline work outside this scope")
-            if 'dinov2' not in dino_model:      # normalize_memory_embs (P/src/model.py:174; im2txtprojection.py:348-349): the CLIP ViTs
+            if dino_model is None or 'dinov2' not in dino_model:      # normalize_memory_embs (P/src/model.py:174; im2txtprojection.py:348-349): the CLIP ViTs
                 bank = bank / bank.norm(dim=-1, keepdim=True)
             if bank.dim() != 2 or bank.shape[1] != self.token_dim:
                 raise ValueError("memory bank is %s, the %s backbone needs [M, %d]" % (tuple(bank.shape), dino_model, self.token_dim))
@@ -416,8 +442,13 @@ class Patchioner(nn.Module):
             # caption_tokens returns the similarities only on the calculate_argmax_text path (model.py:1408-1411); without
             # it the reference fails while unpacking (model.py:1030, 1036)
             raise ValueError("return_n_best_sims needs a model built with calculate_argmax_text")
+        if self.backbone_type == 'AlphaClip' and bboxes is not None and double_DINO_for_bboxes:
+            raise ValueError("double_DINO_for_bboxes is not supported with AlphaClip. AlphaClip processes regions differently.")
         if caption_bboxes_type is not None:
             return self.caption_bboxes(imgs, bboxes, caption_bboxes_type, compute_scores=compute_scores)
+        if self.backbone_type == 'AlphaClip' and (bboxes is not None or traces is not None):
+            # forward_alphaclip_with_regions (P/src/model.py:772-778, 1060-1354): a tower pass per region, the region keys only
+            return self._forward_alphaclip_regions(imgs, bboxes, traces, get_controllable_capts, compute_scores, return_n_best_sims)
 
         eng = self.engine
         outs = {}
@@ -536,6 +567,111 @@ class Patchioner(nn.Module):
         return outs
 
     # ------------------------------------------------------------------------------------------
+    def _alphaclip_region_feats(self, imgs, regions):
+        """Features of AlphaCLIP regions: ``regions`` = (image index, boxes [[x, y, w, h]], points [(x, y)]) per region.  Every region's
+        pixel-level mask is rasterised in one launch, the tower runs over the regions in launches of max_batch sequences (each reads its
+        image in place), and the feature is the CLS row (use_cls_for_localized_captions, the default) or the patch tokens averaged over
+        the patch-level mask, sum(mask * patch) / (sum(mask) + 1e-8) (model.py:1096-1130)."""
+        eng = self.engine
+        R = len(regions)
+        if R == 0:
+            return torch.empty(0, self.token_dim, device=eng.device)
+        tables = [(b, p) for _, b, p in regions]
+        pix = eng.region_masks(tables, self.crop_dim, 1)
+        idx = torch.tensor([i for i, _, _ in regions], dtype=torch.int32)
+        use_cls = self.alphaclip_config.get('use_cls_for_localized_captions', True)
+        cells = None if use_cls else eng.region_masks(tables, self.crop_dim // self.patch_size, self.patch_size).view(R, -1).float()
+        feats = torch.empty(R, self.token_dim, device=eng.device, dtype=torch.float32)
+        # one launch of max_batch regions at a time, each reduced to its features at once: the tokens held never exceed one launch's
+        for s in range(0, R, eng.max_batch):
+            e = min(R, s + eng.max_batch)
+            tokens = eng.vit_forward_regions(imgs, idx[s:e], pix[s:e])
+            if use_cls:
+                feats[s:e] = tokens[:, 0]
+            else:
+                feats[s:e] = eng.region_reduce(tokens, cells[s:e], None, 1.0) / (cells[s:e].sum(dim=1, keepdim=True) + 1e-8)
+        return feats
+
+    def _forward_alphaclip_regions(self, imgs, bboxes, traces, get_controllable_capts, compute_scores, return_n_best_sims):
+        """forward_alphaclip_with_regions (P/src/model.py:1060-1354) with the reference's per-region loop turned into one batch: all
+        regions of the call are rasterised at once, the tower runs over them max_batch at a time, and one caption_tokens call captions
+        them all; the results are re-nested as the reference returns them.  Masks follow alpha_mask_utils.py (boxes with an EXCLUSIVE
+        end, the caller's ``bboxes`` untouched); a dummy box (components summing below 0) gets "" / 0.0 / [] and no pass."""
+        bs = imgs.shape[0]
+        rows = None
+        if bboxes is not None:
+            bt = bboxes if isinstance(bboxes, torch.Tensor) else torch.tensor(bboxes)
+            bt = bt.detach().cpu()
+            rows = [[(float(b.sum()) < 0, [float(v) for v in b.to(torch.float32).tolist()]) for b in bt[i]] for i in range(bs)]
+
+        def points(trace):
+            return [(p['x'], p['y']) for p in trace]
+
+        if get_controllable_capts:
+            regions = []
+            for i in range(bs):
+                boxes = [b for dummy, b in rows[i] if not dummy] if rows is not None else []
+                pts = []
+                if traces is not None:
+                    # traces_to_alpha_mask(traces[i], grid) walks traces[i] as a list of TRACES (alpha_mask_utils.py): with the points of
+                    # one trace there, map_traces_to_grid iterates a point's keys and fails on 'x'['x']
+                    for tr in traces[i]:
+                        if isinstance(tr, dict):
+                            raise TypeError("string indices must be integers (traces_to_alpha_mask takes a list of traces per image)")
+                        pts += points(tr)
+                regions.append((i, boxes, pts))
+            ret = self.caption_tokens(self._alphaclip_region_feats(imgs, regions), compute_scores=compute_scores)
+            return {'set_controllable_capts': ret[0] if compute_scores else ret}
+
+        regions, box_slot = [], []
+        if rows is not None:
+            for i in range(bs):
+                for dummy, b in rows[i]:
+                    box_slot.append(None if dummy else len(regions))
+                    if not dummy:
+                        regions.append((i, [b], []))
+        n_box_regions = len(regions)
+        if traces is not None:
+            for i in range(bs):
+                regions.append((i, [], points(traces[i])))
+        feats = self._alphaclip_region_feats(imgs, regions)
+        caps, scores, sims = [], [], None
+        if return_n_best_sims is None:
+            if len(regions):
+                ret = self.caption_tokens(feats, compute_scores=compute_scores)
+                caps, scores = (ret if compute_scores else (ret, None))
+        else:
+            # the box captions carry their similarities (model.py:1262-1271), the trace captions do not
+            caps, scores, sims = [], [] if compute_scores else None, []
+            if n_box_regions:
+                ret = self.caption_tokens(feats[:n_box_regions].contiguous(), return_n_best_sims=return_n_best_sims, compute_scores=compute_scores)
+                (c, sims), sc = ret if compute_scores else (ret, None)
+                caps += list(c)
+                if compute_scores:
+                    scores += list(sc)
+            if len(regions) > n_box_regions:
+                ret = self.caption_tokens(feats[n_box_regions:].contiguous(), compute_scores=compute_scores)
+                c, sc = ret if compute_scores else (ret, None)
+                caps += list(c)
+                if compute_scores:
+                    scores += list(sc)
+        outs = {}
+        if rows is not None:
+            nb = len(rows[0]) if bs else 0
+            flat_caps = [caps[k] if k is not None else "" for k in box_slot]
+            outs['bbox_capts'] = [flat_caps[i * nb:(i + 1) * nb] for i in range(bs)]
+            if compute_scores:
+                flat = [scores[k] if k is not None else 0.0 for k in box_slot]
+                outs['bbox_scores'] = [flat[i * nb:(i + 1) * nb] for i in range(bs)]
+            if return_n_best_sims is not None:
+                flat = [sims[k] if k is not None else [] for k in box_slot]
+                outs['bbox_sims'] = [flat[i * nb:(i + 1) * nb] for i in range(bs)]
+        if traces is not None:
+            outs['trace_capts'] = list(caps[n_box_regions:])
+            if compute_scores:
+                outs['trace_scores'] = list(scores[n_box_regions:])
+        return outs
+
     def _region_means(self, tokens, variance):
         """compute_region_means (P/src/model.py:45-94)."""
         bs, eng = tokens.shape[0], self.engine
@@ -735,6 +871,8 @@ class Patchioner(nn.Module):
             if v is not None and v is not False:
                 if not (k == "bboxes" and kwargs.get("get_controllable_capts")):
                     raise NotImplementedError("forward_async supports the flat caption outputs only (%s given)" % k)
+        if self.backbone_type == 'AlphaClip' and (kwargs.get("bboxes") is not None or kwargs.get("traces") is not None):
+            raise NotImplementedError("forward_async: AlphaCLIP region captions (a tower pass per region) run through forward() only")
         stream = stream or torch.cuda.current_stream()
         self._defer = True
         try:

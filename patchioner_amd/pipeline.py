@@ -106,6 +106,8 @@ class TraceCaptionPipeline:
         """``stage_replicas``: further Patchioner instances holding the SAME weights (each has its own ViT
         workspace); stage 1 of consecutive batches then alternates over the replicas, each on its own stream,
         so that one batch's GEMM tails, epilogues and launch gaps are filled by the other's kernels."""
+        if getattr(model, "backbone_type", None) == 'AlphaClip':
+            raise NotImplementedError("AlphaCLIP region captions (a tower pass per region) are not pipelined; call forward(traces=...)")
         self.m, self.eng = model, model.engine
         self.stage_models = [model] + list(stage_replicas)
         self.viecap = getattr(model, "viecap", None)

@@ -124,6 +124,101 @@ def synth_clip_vit(seed: int, name: str = "vit_base_patch16_clip_224.openai", de
     return w
 
 
+ALPHACLIP_ARCHS = {
+    # alphaclip_config['name'] (alpha_clip.load names) -> the timm-named OpenAI-CLIP tower of the same shape (CLIP_ARCHS), native crop
+    "ViT-B/16": ("vit_base_patch16_clip_224", 224),
+    "ViT-B/32": ("vit_base_patch32_clip_224", 224),
+    "ViT-L/14": ("vit_large_patch14_clip_224", 224),
+}
+
+
+def alphaclip_arch(name: str):
+    """-> (embed_dim, depth, heads, patch, head width, native crop) of an AlphaCLIP tower name.  Unknown names raise RuntimeError like
+    alpha_clip.load (alpha_clip.py: "Model ... not found")."""
+    if name not in ALPHACLIP_ARCHS:
+        raise RuntimeError("Model %s not found; available models = %s" % (name, list(ALPHACLIP_ARCHS)))
+    timm_name, crop = ALPHACLIP_ARCHS[name]
+    return clip_arch(timm_name) + (crop,)
+
+
+def synth_alphaclip_vit(seed: int, name: str = "ViT-B/16", depth: int | None = None) -> Dict[str, torch.Tensor]:
+    """State dict shaped like AlphaCLIP's ``model.visual.state_dict()`` (P/src/alphaclip/alpha_clip/model.py:336-349, the OpenAI
+    layout with ``attn.in_proj.weight`` as alpha_clip.build_model renames it): conv1 and a NON-ZERO conv1_alpha (trained checkpoints
+    start from zeros and learn it; zeros would hide the alpha path from every test), class_embedding, positional_embedding, ln_pre,
+    transformer.resblocks.{i}.{ln_1, attn.in_proj, attn.out_proj, ln_2, mlp.c_fc, mlp.c_proj}, ln_post, proj [width, output_dim]."""
+    D, full_depth, _, p, out, crop = alphaclip_arch(name)
+    depth = depth or full_depth
+    n = crop // p
+    g = torch.Generator().manual_seed(seed)
+    w: Dict[str, torch.Tensor] = {}
+    w["conv1.weight"] = _tn(g, (D, 3, p, p), 0.02)
+    w["conv1_alpha.weight"] = _tn(g, (D, 1, p, p), 0.05)
+    w["class_embedding"] = _tn(g, (D,), 0.02)
+    w["positional_embedding"] = _tn(g, (1 + n * n, D), 0.02)
+    w["ln_pre.weight"] = 0.5 + torch.rand(D, generator=g)
+    w["ln_pre.bias"] = _tn(g, (D,), 0.02)
+    for i in range(depth):
+        q = "transformer.resblocks.%d." % i
+        for ln in ("ln_1", "ln_2"):
+            w[q + ln + ".weight"] = 0.5 + torch.rand(D, generator=g)
+            w[q + ln + ".bias"] = _tn(g, (D,), 0.02)
+        qkv = _tn(g, (3 * D, D), 0.02)
+        qkv[: 2 * D] *= 2.5
+        w[q + "attn.in_proj.weight"] = qkv
+        w[q + "attn.in_proj.bias"] = _tn(g, (3 * D,), 0.02)
+        w[q + "attn.out_proj.weight"] = _tn(g, (D, D), 0.02) * 0.3
+        w[q + "attn.out_proj.bias"] = _tn(g, (D,), 0.02)
+        w[q + "mlp.c_fc.weight"] = _tn(g, (4 * D, D), 0.02)
+        w[q + "mlp.c_fc.bias"] = _tn(g, (4 * D,), 0.02)
+        w[q + "mlp.c_proj.weight"] = _tn(g, (D, 4 * D), 0.02) * 0.3
+        w[q + "mlp.c_proj.bias"] = _tn(g, (D,), 0.02)
+    w["ln_post.weight"] = 0.5 + torch.rand(D, generator=g)
+    w["ln_post.bias"] = _tn(g, (D,), 0.02)
+    w["proj"] = _tn(g, (D, out), 0.03)
+    return w
+
+
+_ALPHACLIP_BLOCK_KEYS = {"ln_1": "norm1", "ln_2": "norm2", "attn.in_proj": "attn.qkv", "attn.out_proj": "attn.proj",
+                         "mlp.c_fc": "mlp.fc1", "mlp.c_proj": "mlp.fc2"}
+
+
+def alphaclip_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """AlphaCLIP visual state dict (OpenAI layout; ``attn.in_proj.weight`` or the checkpoint's own ``attn.in_proj_weight``; an optional
+    ``visual.`` prefix) -> the engine's keys: the timm names of the CLIP tower (cls_token, pos_embed, patch_embed.proj.weight, norm_pre,
+    blocks.{i}.*, norm, head.weight = proj^T) plus ``patch_embed.alpha.weight`` for conv1_alpha (zeros when the checkpoint has none,
+    alpha_clip/model.py:603-606)."""
+    src = {(k[len("visual."):] if k.startswith("visual.") else k): v for k, v in sd.items()}
+    out: Dict[str, torch.Tensor] = {}
+    for k, v in src.items():
+        k = k.replace("in_proj_weight", "in_proj.weight").replace("in_proj_bias", "in_proj.bias")
+        if k.startswith("transformer.resblocks."):
+            i, rest = k[len("transformer.resblocks."):].split(".", 1)
+            mod, leaf = rest.rsplit(".", 1)
+            if mod not in _ALPHACLIP_BLOCK_KEYS:
+                raise KeyError("unexpected AlphaCLIP block key %r" % k)
+            out["blocks.%s.%s.%s" % (i, _ALPHACLIP_BLOCK_KEYS[mod], leaf)] = v
+        elif k == "conv1.weight":
+            out["patch_embed.proj.weight"] = v
+        elif k == "conv1_alpha.weight":
+            out["patch_embed.alpha.weight"] = v
+        elif k == "class_embedding":
+            out["cls_token"] = v.reshape(1, 1, -1)
+        elif k == "positional_embedding":
+            out["pos_embed"] = v.reshape(1, v.shape[0], v.shape[1])
+        elif k in ("ln_pre.weight", "ln_pre.bias"):
+            out["norm_pre." + k.split(".")[1]] = v
+        elif k in ("ln_post.weight", "ln_post.bias"):
+            out["norm." + k.split(".")[1]] = v
+        elif k == "proj":
+            out["head.weight"] = v.t().contiguous()
+        else:
+            raise KeyError("unexpected AlphaCLIP visual key %r" % k)
+    if "patch_embed.alpha.weight" not in out:
+        pw = out["patch_embed.proj.weight"]
+        out["patch_embed.alpha.weight"] = torch.zeros(pw.shape[0], 1, pw.shape[2], pw.shape[3], dtype=pw.dtype)
+    return out
+
+
 def add_outlier_channels(w: Dict[str, torch.Tensor], channels=(7, 300, 611), block: int = 1, gain: float = 4000.0,
                          hidden_rows=(11, 2000), hidden_gain: float = 30.0) -> Dict[str, torch.Tensor]:
     """DINOv2-like massive activations for stress tests: the MLP branch of ``block`` is multiplied by ``gain`` on a few
