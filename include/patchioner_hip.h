@@ -80,9 +80,17 @@ typedef struct {
    * bias-free head (embed_dim -> vit_out_dim) applied to every token; no qkv hook (has_attention = False, :864-865).
    * 2: AlphaCLIP's ViT (P/src/alphaclip/alpha_clip/model.py:351-380): arch 1 with a fourth, alpha input channel -- conv1(x) +
    * conv1_alpha(alpha) before the position add (weight key patch_embed.alpha.weight [D,1,p,p]); pio_vit_forward is the all-ones
-   * alpha, pio_vit_forward_regions takes a mask per sequence. */
+   * alpha, pio_vit_forward_regions takes a mask per sequence.
+   * 3: RegionCLIP's CLIP ModifiedResNet (P/src/regionclip/clip_backbone.py:112-300, forward_return_spatial_feats with 'res5'):
+   * embed_dim = the attnpool width (32 rn_width), num_heads = embed_dim / 64, patch_size 32, crop_dim a multiple of 32; no
+   * registers, no qkv hook; pio_vit_forward returns [B, 1 + (crop/32)^2, vit_out_dim] L2-normalised attnpool rows.  Weight keys
+   * "rn.*" (weights.regionclip_to_engine: FrozenBN as scale / shift, q|k|v concatenated); depth, pretrain_grid, vit_ln_eps unused. */
   int32_t vit_arch;
   int32_t vit_out_dim;        /* width of the tokens pio_vit_forward returns: 0 = embed_dim; 512 for the CLIP ViT-B head */
+  /* vit_arch 3 only (zero otherwise) */
+  int32_t rn_layers[4];       /* Bottleneck units per stage: (3, 4, 6, 3) RN50, (4, 6, 10, 6) RN50x4 */
+  int32_t rn_width;           /* stem width: 64 RN50, 80 RN50x4 */
+  int32_t rn_attnpool_spatial; /* 1: patch rows = attnpool rows 1.. (use_attnpool_for_spatial_feats); 0: c_proj(x5) without attention */
 } pio_config;
 
 const char* pio_last_error(void);
@@ -453,6 +461,22 @@ int pio_test_layernorm(int32_t operand, const float* x, const float* w, const fl
  * masks [R][S][S] u8 (NULL: ones) -> out [R * (S/p)^2][Kpad] in operand type 0 fp16, 1 bf16, 2 fp32; columns >= 4 p^2 not written. */
 int pio_test_im2col_alpha(int32_t operand, const float* imgs, const int32_t* img_of_region, const uint8_t* masks, int32_t R, int32_t S,
                           int32_t p, int32_t Kpad, void* out, pio_stream stream);
+
+/* RegionCLIP tower kernels (vit_arch 3, csrc/resnet.hip), operand 0 fp16, 1 bf16, 2 exact fp32; all pointers DEVICE.
+ * Convolution (replaces nn.Conv2d + FrozenBatchNorm2d [+ identity] + ReLU of Bottleneck.forward / ModifiedResNet.stem,
+ * P/src/regionclip/clip_backbone.py:57-70, 237-245): x [B][H][W][Cin] NHWC, Cin % 8 == 0, w [Cout][ks][ks][Cin], ks 1 or 3 (pad
+ * ks / 2), stride >= 1; y [B][Ho][Wo][Cout] operand type = relu?(rnd(rnd(rnd(conv) * scale + shift) + res)) with res [B][Ho][Wo][Cout]
+ * or NULL; with y32 non-NULL (y NULL, res NULL) the same value before the residual, as fp32.  tile 0 = the forward's choice, 1 = 64 x
+ * 64, 2 = 128 x 128 workgroups (ignored in fp32). */
+int pio_test_conv(int32_t operand, const void* x, const void* w, const float* scale, const float* shift, const void* res, void* y,
+                  float* y32, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t ks, int32_t stride, int32_t relu,
+                  int32_t tile, pio_stream stream);
+/* nn.AvgPool2d(2) in NHWC: x [B][H][W][C] -> y [B][H/2][W/2][C] (clip_backbone.py:35, 55, 157) */
+int pio_test_avgpool(int32_t operand, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, void* y, pio_stream stream);
+/* AttentionPool2d's input rows (clip_backbone.py:84-86): x [B][HW][C], pos [1 + HW][C] fp32 -> out [B][Tp][C]: row 0 = mean + pos[0],
+ * rows 1..HW = x + pos[1..], zero rows to Tp */
+int pio_test_attnpool_in(int32_t operand, const void* x, const float* pos, int32_t B, int32_t HW, int32_t C, int32_t Tp, void* out,
+                         pio_stream stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,7 @@ class PioConfig(ctypes.Structure):
         ("max_batch", c_int32), ("max_prefixes", c_int32), ("max_steps", c_int32),
         ("vit_operand_type", c_int32), ("device", c_int32),
         ("vit_arch", c_int32), ("vit_out_dim", c_int32),
+        ("rn_layers", c_int32 * 4), ("rn_width", c_int32), ("rn_attnpool_spatial", c_int32),
     ]
 
 
@@ -132,6 +133,10 @@ SIGNATURES = {
     "pio_test_layernorm": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                      c_int32, c_void_p]),
     "pio_test_im2col_alpha": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "pio_test_conv": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "pio_test_avgpool": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "pio_test_attnpool_in": (c_int32, [c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

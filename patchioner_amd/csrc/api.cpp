@@ -16,6 +16,7 @@
 #include "common.h"
 #include "host_prep.h"
 #include "kernels.h"
+#include "resnet.h"
 
 using namespace pio;
 
@@ -100,8 +101,15 @@ hipError_t launch_im2col_alpha(int, const float*, const int32_t*, const uint8_t*
 hipError_t launch_region_masks(const float*, const int32_t*, const double*, const int32_t*, int, int, float, uint8_t*, hipStream_t) __attribute__((weak));
 }  // namespace pio
 #define PIO_ALPHA_LINKED (&launch_im2col_alpha != nullptr && &launch_region_masks != nullptr)
+namespace pio {
+int rn_build(const pio_config&, const RnGet&, RnNet**) __attribute__((weak));
+void rn_destroy(RnNet*) __attribute__((weak));
+int rn_forward(RnNet*, const float*, int, float*, hipStream_t) __attribute__((weak));
+}  // namespace pio
+#define PIO_RN_LINKED (&rn_build != nullptr && &rn_destroy != nullptr && &rn_forward != nullptr)
 #else
 #define PIO_ALPHA_LINKED true
+#define PIO_RN_LINKED true
 #endif
 
 struct pio_context {
@@ -121,6 +129,7 @@ struct pio_context {
   float* vhead_w = nullptr;                      // CLIP: head.weight [vit_out_dim][D], fp32
   float* ones = nullptr;                         // CLIP: "LayerScale" of ones (x += 1 * branch is exact)
   float* tok_tmp = nullptr;                      // CLIP: final-norm tokens [max_batch * T][D] before the head
+  RnNet* rn = nullptr;                           // vit_arch 3: the RegionCLIP ResNet tower (resnet_api.cpp owns its memory)
   int Dout = 0;                                  // width of the returned tokens
   // exact-fp32 parity mode (vit_operand_type = 2, vit_fp32.hip): fp32 copies of the GEMM weights and fp32 activations
   bool vit_f32 = false;
@@ -652,7 +661,7 @@ bool is_known_key(const std::string& k) {
                                 "talk2dino.b"};
   for (auto e : exact) if (k == e) return true;
   return k.rfind("blocks.", 0) == 0 || k.rfind("decoder.transformer.", 0) == 0 || k.rfind("clip_project.model.0.", 0) == 0 ||
-         k.rfind("mapping_network.", 0) == 0;
+         k.rfind("mapping_network.", 0) == 0 || k.rfind("rn.", 0) == 0;
 }
 
 // ---- Pillow's resampling coefficients (src/libImaging/Resample.c: bicubic_filter, precompute_coeffs,
@@ -755,12 +764,20 @@ int pio_create(const pio_config* cfg, pio_handle* out) {
     return fail(PIO_ERR_INVALID_ARG, "pio_create: capacities out of range (prefixes <= 256, decoder positions <= 256)");
   if (cfg->readout_heads != 16 && cfg->readout_heads * 64 != cfg->embed_dim)
     return fail(PIO_ERR_INVALID_ARG, "pio_create: readout_heads must be 16, or embed_dim / 64 (ViT-S: 6)");
-  if (cfg->vit_arch < 0 || cfg->vit_arch > 2)
-    return fail(PIO_ERR_INVALID_ARG, "pio_create: vit_arch must be 0 (DINOv2), 1 (OpenAI-CLIP ViT) or 2 (AlphaCLIP ViT)");
+  if (cfg->vit_arch < 0 || cfg->vit_arch > 3)
+    return fail(PIO_ERR_INVALID_ARG, "pio_create: vit_arch must be 0 (DINOv2), 1 (OpenAI-CLIP ViT), 2 (AlphaCLIP ViT) or 3 (RegionCLIP ResNet)");
+  if (cfg->vit_arch == 3) {
+    bool ok = cfg->rn_width >= 8 && cfg->rn_width % 16 == 0 && cfg->embed_dim == 32 * cfg->rn_width && cfg->patch_size == 32 &&
+              (cfg->rn_attnpool_spatial == 0 || cfg->rn_attnpool_spatial == 1);
+    for (int i = 0; i < 4; ++i) ok = ok && cfg->rn_layers[i] >= 1;
+    if (!ok)
+      return fail(PIO_ERR_INVALID_ARG, "pio_create: vit_arch 3 needs rn_layers >= 1, rn_width a multiple of 16, embed_dim = 32 rn_width, "
+                                       "patch_size 32, rn_attnpool_spatial 0 or 1");
+  }
   if (cfg->vit_arch >= 1 && cfg->num_registers != 0)
     return fail(PIO_ERR_INVALID_ARG, "pio_create: the CLIP ViT has no registers");
   if (cfg->vit_out_dim < 0 || (cfg->vit_out_dim > 0 && cfg->vit_out_dim % 32 != 0) || (cfg->vit_arch == 0 && cfg->vit_out_dim != 0 && cfg->vit_out_dim != cfg->embed_dim))
-    return fail(PIO_ERR_INVALID_ARG, "pio_create: vit_out_dim must be 0, or a multiple of 32 with vit_arch 1 or 2");
+    return fail(PIO_ERR_INVALID_ARG, "pio_create: vit_out_dim must be 0, or a multiple of 32 with vit_arch 1, 2 or 3");
   int ndev = 0;
   HIP_OK(hipGetDeviceCount(&ndev));
   if (cfg->device < 0 || cfg->device >= ndev) return fail(PIO_ERR_INVALID_ARG, "pio_create: no such HIP device");
@@ -847,6 +864,7 @@ int pio_destroy(pio_handle c) {
   for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.second);
   for (auto& g : c->pgraphs) { (void)hipGraphExecDestroy(g.second.exec); if (g.second.done) (void)hipEventDestroy(g.second.done); }
   for (void* p : c->allocs) (void)hipFree(p);
+  if (c->rn && PIO_RN_LINKED) rn_destroy(c->rn);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   for (auto& sl : c->prep_slots) {
     if (sl.host) (void)hipHostFree(sl.host);
@@ -881,7 +899,18 @@ int pio_finalize_weights(pio_handle c) {
   if (c->finalized) return fail(PIO_ERR_INVALID_ARG, "pio_finalize_weights: called twice");
   HIP_OK(hipSetDevice(c->cfg.device));
   int rc;
-  if (find(c, "cls_token")) {
+  if (c->cfg.vit_arch == 3 && find(c, "rn.conv1.weight")) {
+    // RegionCLIP's ResNet tower: resnet_api.cpp packs it, every key through need()'s shape check
+    if (!PIO_RN_LINKED) return fail(PIO_ERR_NOT_READY, "pio_finalize_weights: the ResNet tower is not linked");
+    const RnGet get = [c](const std::string& key, int64_t numel, const float** data) {
+      const HostTensor* t;
+      const int r = need(c, key, {numel}, &t);
+      if (r == PIO_OK) *data = t->data.data();
+      return r;
+    };
+    if ((rc = rn_build(c->cfg, get, &c->rn))) return rc;
+    c->has_vit = true;
+  } else if (c->cfg.vit_arch != 3 && find(c, "cls_token")) {
     if ((rc = finalize_vit(c))) return rc;
   }
   if (find(c, "decoder.transformer.wte.weight")) {
@@ -942,7 +971,7 @@ static int bank_common(pio_context* c, int64_t rows, int32_t dim) {
 
 int pio_set_memory_bank(pio_handle c, const float* host_bank, int64_t rows, int32_t dim, int64_t* rows_kept) {
   if (!c || !host_bank || rows < 1) return fail(PIO_ERR_INVALID_ARG, "pio_set_memory_bank: bad argument");
-  if (dim != 384 && dim != 512 && dim != 768) return fail(PIO_ERR_SHAPE, "memory bank dim must be 384, 512 or 768");
+  if (dim != 384 && dim != 512 && dim != 640 && dim != 768 && dim != 1024) return fail(PIO_ERR_SHAPE, "memory bank dim must be 384, 512, 640, 768 or 1024");
   if (c->bank) return fail(PIO_ERR_INVALID_ARG, "memory bank already set");
   HIP_OK(hipSetDevice(c->cfg.device));
   // the reference drops rows whose norm is 0 when it loads the bank (im2txtprojection.py:343-345)
@@ -978,7 +1007,7 @@ int pio_set_memory_bank(pio_handle c, const float* host_bank, int64_t rows, int3
 
 int pio_set_memory_bank_device(pio_handle c, const float* dev_bank, int64_t rows, int32_t dim) {
   if (!c || !dev_bank || rows < 1) return fail(PIO_ERR_INVALID_ARG, "pio_set_memory_bank_device: bad argument");
-  if (dim != 384 && dim != 512 && dim != 768) return fail(PIO_ERR_SHAPE, "memory bank dim must be 384, 512 or 768");
+  if (dim != 384 && dim != 512 && dim != 640 && dim != 768 && dim != 1024) return fail(PIO_ERR_SHAPE, "memory bank dim must be 384, 512, 640, 768 or 1024");
   if (c->bank) return fail(PIO_ERR_INVALID_ARG, "memory bank already set");
   HIP_OK(hipSetDevice(c->cfg.device));
   int rc;
@@ -1130,6 +1159,7 @@ int pio_vit_forward(pio_handle c, const float* imgs, int32_t B, float* tokens, f
   if (!c->has_vit) return fail(PIO_ERR_NOT_READY, "pio_vit_forward: backbone weights not loaded");
   if (B < 1 || B > c->cfg.max_batch) return fail(PIO_ERR_CAPACITY, "pio_vit_forward: batch above max_batch");
   HIP_OK(hipSetDevice(c->cfg.device));
+  if (c->cfg.vit_arch == 3) return rn_forward(c->rn, imgs, B, tokens, (hipStream_t)stream);
   return vit_forward_impl(c, imgs, B, nullptr, nullptr, tokens, qkv_last, (hipStream_t)stream);
 }
 

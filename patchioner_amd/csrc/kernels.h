@@ -140,6 +140,28 @@ hipError_t launch_box_seq_reduce(const float* x, const int32_t* lens, int Ns, in
 hipError_t launch_token_init(float* x, const float* cls, const float* pos0, const float* reg, int B, int R, int T,
                              int Tp, int D, hipStream_t s);
 
+// ---- resnet.hip: RegionCLIP's CLIP ModifiedResNet tower (vit_arch 3); type 0 fp16, 1 bf16, 2 exact fp32 (the parity mode)
+struct ConvArgs {
+  const void* x;        // [B][H][W][Cin] (Cin padded to a multiple of 8; the padding channels are zero)
+  const void* w;        // [Cout][ks][ks][Cin]
+  const float* scale;   // [Cout] FrozenBN weight / sqrt(var + eps)
+  const float* shift;   // [Cout] bias - mean * scale
+  const void* res;      // [M][Cout] residual added after the BN (null: none)
+  void* y;              // [B][Ho][Wo][Cout] (operand type)
+  float* y32;           // out_f32: fp32 rows, see resnet.hip conv_store
+  int B, H, W, Cin, Cout, ks, stride, pad, Ho, Wo;
+  int relu;
+  int out_f32, out_rows, out_off, valid;
+};
+// tile 0: route_conv's choice, 1: 64 x 64 workgroups, 2: 128 x 128 (the bits do not depend on it)
+int route_conv(const ConvArgs& a);
+hipError_t launch_conv(int type, const ConvArgs& a, int tile, hipStream_t s);
+// imgs [B][3][S][S] fp32 -> [B][S][S][8] (channels 3..7 zero)
+hipError_t launch_rn_input(int type, const float* imgs, int B, int S, void* out, hipStream_t s);
+hipError_t launch_avgpool2(int type, const void* x, int B, int H, int W, int C, void* y, hipStream_t s);
+// x [B][HW][C] -> out [B][Tp][C]: row 0 = mean over HW + pos[0], rows 1..HW = x + pos[1..], zero rows to Tp (pos fp32 [1 + HW][C])
+hipError_t launch_attnpool_in(int type, const void* x, const float* pos, int B, int HW, int C, int Tp, void* out, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------
 // attention read-out and region weighting (all fp32)
 // ---------------------------------------------------------------------------------------------

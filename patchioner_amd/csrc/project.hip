@@ -629,6 +629,9 @@ static hipError_t project_pass_d(const ProjectArgs& a, int q0, int parts, hipStr
       case 384: return split ? project_pass<384, NQG, true>(a, q0, parts, s) : project_pass<384, NQG, false>(a, q0, parts, s);
       case 512: return split ? project_pass<512, NQG, true>(a, q0, parts, s) : project_pass<512, NQG, false>(a, q0, parts, s);
       case 768: return split ? project_pass<768, NQG, true>(a, q0, parts, s) : project_pass<768, NQG, false>(a, q0, parts, s);
+      // RegionCLIP's attnpool widths (RN50x4 640, RN50 1024): the same kernel, its 1 KiB DMA operations masked past the row's end
+      case 640: return split ? project_pass<640, NQG, true>(a, q0, parts, s) : project_pass<640, NQG, false>(a, q0, parts, s);
+      case 1024: return split ? project_pass<1024, NQG, true>(a, q0, parts, s) : project_pass<1024, NQG, false>(a, q0, parts, s);
       default: return hipErrorInvalidValue;
     }
   }

@@ -142,4 +142,41 @@ int pio_test_im2col_alpha(int32_t operand, const float* imgs, const int32_t* img
   return PIO_OK;
 }
 
+int pio_test_conv(int32_t operand, const void* x, const void* w, const float* scale, const float* shift, const void* res, void* y,
+                  float* y32, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t ks, int32_t stride, int32_t relu,
+                  int32_t tile, pio_stream stream) {
+  if (operand < 0 || operand > 2) return fail(PIO_ERR_INVALID_ARG, "pio_test_conv: operand 0 (fp16), 1 (bf16) or 2 (fp32)");
+  if (!x || !w || !scale || !shift || (y == nullptr) == (y32 == nullptr) || (y32 && res))
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_conv: x, w, scale, shift and exactly one of y / y32 (y32: no residual)");
+  if (B < 1 || H < 1 || W < 1 || Cin < 8 || Cin % 8 != 0 || Cout < 1 || (ks != 1 && ks != 3) || stride < 1 || tile < 0 || tile > 2)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_conv: B, H, W >= 1, Cin % 8 == 0, ks 1 or 3, stride >= 1, tile 0..2");
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.res = res; a.y = y; a.y32 = y32;
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ks = ks; a.stride = stride; a.pad = ks / 2;
+  a.Ho = (H + 2 * a.pad - ks) / stride + 1; a.Wo = (W + 2 * a.pad - ks) / stride + 1; a.relu = relu;
+  if (y32) { a.out_f32 = 1; a.out_rows = a.Ho * a.Wo; a.out_off = 0; a.valid = a.Ho * a.Wo; }
+  const hipError_t e = launch_conv(operand, a, tile, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_conv: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_conv: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_avgpool(int32_t operand, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, void* y, pio_stream stream) {
+  if (operand < 0 || operand > 2 || !x || !y || B < 1 || H < 2 || W < 2 || C < 1)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_avgpool: operand 0..2, x, y, B >= 1, H, W >= 2, C >= 1");
+  const hipError_t e = launch_avgpool2(operand, x, B, H, W, C, y, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_avgpool: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_attnpool_in(int32_t operand, const void* x, const float* pos, int32_t B, int32_t HW, int32_t C, int32_t Tp, void* out,
+                         pio_stream stream) {
+  if (operand < 0 || operand > 2 || !x || !pos || !out || B < 1 || HW < 1 || C < 1 || Tp < HW + 1)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_attnpool_in: operand 0..2, x, pos, out, B, HW, C >= 1, Tp > HW");
+  const hipError_t e = launch_attnpool_in(operand, x, pos, B, HW, C, Tp, out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_attnpool_in: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
 }  // extern "C"

@@ -27,7 +27,8 @@ class Engine:
                  dec_heads: int = 4, dec_embd: int = 768, dec_vocab: int = 50257, dec_positions: int = 1024,
                  max_batch: int = 16, max_prefixes: int = 64, max_steps: int = 30, vit_dtype: str = "fp16",
                  device_index: int = 0, readout_heads: int = 16, readout_scale: float = 0.125, vit_arch: str = "dinov2",
-                 vit_out_dim: int = 0, vit_ln_eps: float = 1e-6):
+                 vit_out_dim: int = 0, vit_ln_eps: float = 1e-6, rn_layers=(0, 0, 0, 0), rn_width: int = 0,
+                 rn_attnpool_spatial: bool = True):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise PioError(-101, "no HIP device visible: the captioning path has no CPU fallback")
@@ -39,7 +40,8 @@ class Engine:
             dec_embd=dec_embd, dec_vocab=dec_vocab, dec_positions=dec_positions, prefix_size=prefix_size,
             dec_ln_eps=1e-5, max_batch=max_batch, max_prefixes=max_prefixes, max_steps=max_steps,
             vit_operand_type={"fp16": 0, "bf16": 1, "fp32": 2}[vit_dtype], device=device_index,
-            vit_arch={"dinov2": 0, "clip": 1, "alphaclip": 2}[vit_arch], vit_out_dim=vit_out_dim)
+            vit_arch={"dinov2": 0, "clip": 1, "alphaclip": 2, "regionclip": 3}[vit_arch], vit_out_dim=vit_out_dim,
+            rn_layers=(ctypes.c_int32 * 4)(*rn_layers), rn_width=rn_width, rn_attnpool_spatial=int(bool(rn_attnpool_spatial)))
         self.cfg = cfg
         h = ctypes.c_void_p()
         check(self.lib.pio_create(ctypes.byref(cfg), ctypes.byref(h)))

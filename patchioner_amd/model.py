@@ -39,7 +39,7 @@ from .engine import Engine
 from .preprocess import make_transforms
 from .tokenizer import ClipDetokenizer
 
-_OUT_OF_SCOPE = ("proxyclip_clipmodel", "regionclip_config", "invite_config", "denseclip_config", "clipcap_config")
+_OUT_OF_SCOPE = ("proxyclip_clipmodel", "invite_config", "denseclip_config", "clipcap_config")
 
 
 def _load_state_dict(spec):
@@ -82,6 +82,51 @@ def _load_memory_bank(spec):
     raise ValueError("unsupported memory bank format: %r" % (spec,))
 
 
+def _regionclip_setup(rc: dict, dino_model, crop_dim: int, synthetic_seed, online_texts) -> dict:
+    """RegionCLIP's ModifiedResNet (P/src/model.py:427-457; regionclip/loader.py:39-231): checks the config, loads the checkpoint
+    (``checkpoint``: a RegionCLIP ``backbone.*`` checkpoint or a CLIP ``visual.*`` dict; else synthetic weights from
+    synthetic_seed) and returns the engine's weights with the tower's sizes.  Everything is checked before the device is touched."""
+    resnets = rc.get('MODEL', {}).get('RESNETS', {})
+    out_features = resnets.get('OUT_FEATURES', ['res4'])          # build_model_with_defaults' default (loader.py:158)
+    if 'res5' not in out_features:
+        raise NotImplementedError("RegionCLIP with OUT_FEATURES %r: without 'res5' the reference returns layer3's stride-16 grid, which "
+                                  "disagrees with its own num_patch_tokens (crop / 32)^2 (clip_backbone.py:278-299)" % (out_features,))
+    if online_texts is not None:
+        raise NotImplementedError("online_texts with RegionCLIP: the bank would come from RegionCLIP's own text tower, which this build "
+                                  "does not implement; pass the bank as a file or tensor (memory_bank)")
+    if rc.get('patch_size', 32) != 32:
+        raise NotImplementedError("regionclip_config patch_size %r: the res5 grid is crop / 32, patch_size must be 32" % (rc['patch_size'],))
+    if crop_dim % 32 != 0:
+        raise ValueError("crop_dim must be a multiple of 32 for the RegionCLIP ResNet")
+    sd = _load_state_dict(rc.get('checkpoint', None)) if rc.get('checkpoint', None) is not None else None
+    res = resnets.get('IMAGE_RESOLUTION', None)
+    if sd is None:
+        if synthetic_seed is None:
+            raise FileNotFoundError("regionclip_config['checkpoint'] is required (or synthetic_seed)")
+        name = rc.get('name') or ("RN50x4" if "50x4" in (dino_model or "") or resnets.get('DEPTH') == 200 else "RN50")
+        sd = W.synth_regionclip_rn(synthetic_seed + 1, name, image_resolution=res or 224)
+    layers, width, grid, out_dim = W.regionclip_layers(sd)
+    embed = 32 * width                        # attnpool width and heads as the reference derives them (clip_backbone.py:198-200, 705)
+    heads = embed // 64
+    if res is None:
+        res = grid * 32
+    s = res // 32
+    pos = None
+    if res / 32 != grid:
+        # build_model_with_defaults (loader.py:200-210) drops the checkpoint's table; the tower keeps AttentionPool2d.__init__'s
+        # unseeded draw randn(s^2 + 1, C) / sqrt(C) (clip_backbone.py:76).  Drawn here from torch's default CPU generator: the reference
+        # draws it after the rest of the model's initialisation, so its own values cannot be replayed bit for bit
+        print("Warning: Removing incompatible positional embedding from checkpoint.")
+        print(f"  Checkpoint spatial size: {grid}x{grid} (for image resolution {grid * 32})")
+        print(f"  Config image resolution: {res} (requires {res // 32}x{res // 32})")
+        pos = torch.randn(s * s + 1, embed) / embed ** 0.5
+    if s != crop_dim // 32:
+        raise RuntimeError("The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 0: the attnpool "
+                           "table is built for IMAGE_RESOLUTION %d" % ((crop_dim // 32) ** 2 + 1, s * s + 1, res))
+    return dict(sd=W.regionclip_to_engine(sd, pos=pos), layers=layers, width=width, embed=embed, heads=heads, out_dim=out_dim,
+                spatial_attn=bool(rc.get('use_attnpool_for_spatial_feats', True)))
+
+
 class Patchioner(nn.Module):
 
     def __init__(self, decoder_weights, device, prefix_size, linear_talk2dino, support_memory_size, projection_type=None,
@@ -94,8 +139,7 @@ class Patchioner(nn.Module):
                  vit_dtype="fp16", memory_bank_texts=None, clip_text_weights=None, clip_text_dtype="fp16",
                  talk2dino_projection_weights=None, **kwargs):
         super().__init__(**kwargs)
-        given = dict(proxyclip_clipmodel=proxyclip_clipmodel,
-                     regionclip_config=regionclip_config, invite_config=invite_config,
+        given = dict(proxyclip_clipmodel=proxyclip_clipmodel, invite_config=invite_config,
                      denseclip_config=denseclip_config, clipcap_config=clipcap_config)
         for k in _OUT_OF_SCOPE:
             if given[k] is not None:
@@ -108,7 +152,10 @@ class Patchioner(nn.Module):
         if online_texts is not None and support_memory_size > 0 and len(online_texts) == 0:
             raise ValueError("online_texts is empty")
         is_alpha = alphaclip_config is not None
+        is_region = regionclip_config is not None
         alpha_sd = None
+        if is_region:
+            rn = _regionclip_setup(regionclip_config, dino_model, crop_dim, synthetic_seed, online_texts)
         if is_alpha:
             # P/src/model.py:515-545 (alphaclip_loader.load_alphaclip): AlphaCLIP's ViT, the OpenAI-CLIP tower with an alpha input
             # channel.  Name, crop and weights are checked here, before anything touches the device.
@@ -131,7 +178,7 @@ class Patchioner(nn.Module):
         # P/src/model.py:339-392: 'dinov2' names load from torch.hub, 'openai' names are the timm OpenAI-CLIP towers of the
         # "DeCap original" configurations (configs/decap_B16*.k.yaml, decap_B32.k.yaml)
         is_clip = dino_model is not None and 'openai' in dino_model and 'dinov2' not in dino_model
-        if is_alpha:
+        if is_alpha or is_region:
             pass
         elif dino_model is None or 'dinotxt' in dino_model or not ('dinov2' in dino_model or is_clip):
             raise ValueError("Unsupported backbone %r: this build implements the DINOv2 ViT-S/B/L-14 family and the timm "
@@ -168,8 +215,16 @@ class Patchioner(nn.Module):
         self.resize_dim = resize_dim
         self.crop_dim = crop_dim
         self.model_name = dino_model
-        self.num_global_tokens = 1 if is_alpha or "reg" not in dino_model else 5
-        if is_alpha:
+        # RegionCLIP: 5, as the reference's `"reg" in dino_model` makes it for 'regionclip_*' names (model.py:198) -- read only by the
+        # attention read-out, which this backbone never reaches; its tokens are 1 cls row + n^2 patches (self._G)
+        self.num_global_tokens = 1 if is_alpha or dino_model is None or "reg" not in dino_model else 5
+        self._G = 1 if is_region else self.num_global_tokens
+        if is_region:
+            # model.py:214-216, 254-263: patch_size and embed_dim come from the config; the tokens are the attnpool's output width
+            depth, heads, patch_size, self.token_dim = sum(rn["layers"]), rn["heads"], 32, rn["out_dim"]
+            self.embed_dim = regionclip_config.get('embed_dim', 1024)
+            self.regionclip_config = dict(regionclip_config)
+        elif is_alpha:
             # the tower is alpha_dv wide; the reference's embed_dim is alphaclip_config['embed_dim'] (model.py:305-310), the head's width
             depth, heads, patch_size, self.token_dim = 0, alpha_heads, alpha_p, alpha_out
             self.embed_dim = alphaclip_config.get('embed_dim', alpha_out)
@@ -187,24 +242,25 @@ class Patchioner(nn.Module):
             raise ValueError("crop_dim must be a multiple of %d (the reference's reshape fails otherwise)" % patch_size)
         self.num_patch_tokens = crop_dim // patch_size * crop_dim // patch_size
         self.num_tokens = self.num_global_tokens + self.num_patch_tokens
-        self.num_attn_heads = 16 if is_alpha or 'vits' not in dino_model else 6
+        self.num_attn_heads = 16 if is_alpha or is_region or 'vits' not in dino_model else 6
         self.scale = 0.125
         self.patch_size = patch_size
-        self.backbone_type = 'AlphaClip' if is_alpha else ('CLIP' if is_clip else 'DINO')            # model.py:650-651, :786, :642-644
-        if is_clip or is_alpha:
+        self.backbone_type = 'RegionCLIP' if is_region else ('AlphaClip' if is_alpha else ('CLIP' if is_clip else 'DINO'))  # model.py:634-651
+        if is_clip or is_alpha or is_region:
             from .preprocess import CLIP_MEAN, CLIP_STD
             self.image_transforms, self.image_transforms_no_crop = make_transforms(resize_dim, crop_dim, CLIP_MEAN, CLIP_STD)
         else:
             self.image_transforms, self.image_transforms_no_crop = make_transforms(resize_dim, crop_dim)
 
-        vit_sd = alpha_sd if is_alpha else _load_state_dict(dino_weights)
+        vit_sd = rn["sd"] if is_region else (alpha_sd if is_alpha else _load_state_dict(dino_weights))
         if vit_sd is None:
             if synthetic_seed is None:
                 raise FileNotFoundError("dino_weights is required: torch.hub.load('facebookresearch/dinov2', ...) / "
                                         "timm.create_model(..., pretrained=True) need network, which this target does not have")
             vit_sd = W.synth_clip_vit(synthetic_seed + 1, dino_model) if is_clip else W.synth_dinov2(synthetic_seed + 1, dino_model)
-        depth = 1 + max(int(k.split(".")[1]) for k in vit_sd if k.startswith("blocks."))
-        if attention_type != 'qkv' and not is_clip and not is_alpha:
+        if not is_region:
+            depth = 1 + max(int(k.split(".")[1]) for k in vit_sd if k.startswith("blocks."))
+        if attention_type != 'qkv' and not is_clip and not is_alpha and not is_region:
             # the reference re-orders the last block's fused q|k|v rows (P/src/model.py:569-582)
             vit_sd = dict(vit_sd)
             D = self.embed_dim
@@ -243,13 +299,19 @@ class Patchioner(nn.Module):
             dec_kw = dict(dec_layers=n_layer, dec_heads=12, max_steps=256,
                           dec_vocab=int(viecap_sd["gpt.transformer.wte.weight"].shape[0]),
                           dec_positions=int(viecap_sd["gpt.transformer.wpe.weight"].shape[0]))
-        self.engine = Engine(embed_dim=alpha_dv if is_alpha else self.embed_dim, depth=depth, num_heads=heads,
-                             num_registers=self.num_global_tokens - 1, crop_dim=crop_dim, patch_size=patch_size,
-                             pretrain_grid=int(math.isqrt(vit_sd["pos_embed"].shape[1] - 1)), prefix_size=prefix_size,
+        if is_region:
+            arch_kw = dict(embed_dim=rn["embed"], num_registers=0, pretrain_grid=crop_dim // 32, vit_arch="regionclip",
+                           vit_out_dim=rn["out_dim"], vit_ln_eps=1e-5, rn_layers=rn["layers"], rn_width=rn["width"],
+                           rn_attnpool_spatial=rn["spatial_attn"])
+        else:
+            arch_kw = dict(embed_dim=alpha_dv if is_alpha else self.embed_dim, num_registers=self.num_global_tokens - 1,
+                           pretrain_grid=int(math.isqrt(vit_sd["pos_embed"].shape[1] - 1)),
+                           vit_arch="alphaclip" if is_alpha else ("clip" if is_clip else "dinov2"),
+                           vit_out_dim=self.token_dim if is_clip or is_alpha else 0, vit_ln_eps=1e-5 if is_clip or is_alpha else 1e-6)
+        self.engine = Engine(depth=depth, num_heads=heads, crop_dim=crop_dim, patch_size=patch_size, prefix_size=prefix_size,
                              max_batch=max_batch, max_prefixes=max_prefixes, vit_dtype=vit_dtype,
                              device_index=self._device.index, readout_heads=self.num_attn_heads, readout_scale=self.scale,
-                             vit_arch="alphaclip" if is_alpha else ("clip" if is_clip else "dinov2"),
-                             vit_out_dim=self.token_dim if is_clip or is_alpha else 0, vit_ln_eps=1e-5 if is_clip or is_alpha else 1e-6, **dec_kw)
+                             **arch_kw, **dec_kw)
         self.engine.load_state_dict(vit_sd)
         if dec_sd is not None:                         # calculate_argmax_text without decoder weights: no decoder (model.py:165)
             self.engine.load_state_dict(dec_sd)        # strict=False like the reference (decap.py:214)
@@ -460,7 +522,7 @@ class Patchioner(nn.Module):
         if double_DINO_for_bboxes and not has_attention:
             raise AttributeError("double_DINO_for_bboxes re-runs a DINOv2 block (bbox_utils.py:300-403): not a %s backbone" % self.backbone_type)
         tokens, qkv = eng.vit_forward(imgs, want_qkv=has_attention)
-        G = self.num_global_tokens
+        G = self._G
         embed_dim = tokens.shape[-1]                 # model.py:924: the width of x_norm_patchtokens (512 behind the CLIP head)
         clean_avg = cleaning_type is not None and clean_from == "avg_self_attn" and has_attention
         if has_attention:

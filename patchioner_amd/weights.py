@@ -10,7 +10,7 @@ All generators use a CPU ``torch.Generator`` so the numbers are identical on eve
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
@@ -461,3 +461,141 @@ def synth_bpe(seed: int = 0, merges: int = 400):
                 else:
                     i += 1
     return vocab, merge_list
+
+
+# ---- RegionCLIP: CLIP's ModifiedResNet (P/src/regionclip/clip_backbone.py:112-300, loader.py:60-231) ----
+# name -> (Bottleneck units per stage, stem width, attnpool width, heads, output width); heads = width * 32 // 64 (clip_backbone.py:705)
+_REGIONCLIP_ARCH = {"RN50": ((3, 4, 6, 3), 64, 2048, 32, 1024), "RN50x4": ((4, 6, 10, 6), 80, 2560, 40, 640)}
+FROZEN_BN_EPS = 1e-5     # detectron2.layers.FrozenBatchNorm2d(num_features, eps=1e-5)
+
+
+def regionclip_arch(spec):
+    """``spec``: "RN50" / "RN50x4", a detectron2 RESNETS.DEPTH (50 / 200, clip_backbone.py:183-192) or the (4,) layer counts
+    -> (layers, width, embed_dim, heads, output_dim)."""
+    if isinstance(spec, int):
+        spec = {50: "RN50", 200: "RN50x4"}.get(spec, spec)
+    if isinstance(spec, (tuple, list)):
+        for v in _REGIONCLIP_ARCH.values():
+            if tuple(spec) == v[0]:
+                return v
+        raise ValueError("RegionCLIP layers %r: this build knows RN50 %r and RN50x4 %r" % (tuple(spec), _REGIONCLIP_ARCH["RN50"][0],
+                                                                                          _REGIONCLIP_ARCH["RN50x4"][0]))
+    if spec not in _REGIONCLIP_ARCH:
+        raise ValueError("RegionCLIP backbone %r: this build knows RN50 and RN50x4" % (spec,))
+    return _REGIONCLIP_ARCH[spec]
+
+
+def _rn_strip(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The visual tower's keys without their prefix: a RegionCLIP checkpoint's ``backbone.*`` (under 'model' or 'state_dict',
+    loader.py:85-110) or a plain CLIP dict's ``visual.*``; the text tower's keys are dropped."""
+    for wrap in ("model", "state_dict"):
+        if wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+    out = {}
+    for k, v in sd.items():
+        for pre in ("backbone.", "visual."):
+            if k.startswith(pre):
+                out[k[len(pre):]] = v
+    if not out:
+        raise KeyError("no 'backbone.*' or 'visual.*' keys: not a RegionCLIP / CLIP ResNet checkpoint")
+    return out
+
+
+def regionclip_layers(sd: Dict[str, torch.Tensor]):
+    """(layer counts, stem width, attnpool grid side, output width) of a tower's state dict (loader.py:193-199, 207)."""
+    v = _rn_strip(sd)
+    counts = tuple(len({k.split(".")[1] for k in v if k.startswith("layer%d." % b)}) for b in (1, 2, 3, 4))
+    width = int(v["layer1.0.conv1.weight"].shape[0])
+    grid = round((v["attnpool.positional_embedding"].shape[0] - 1) ** 0.5)
+    return counts, width, grid, int(v["attnpool.c_proj.weight"].shape[0])
+
+
+def frozen_bn_affine(w, b, mean, var, eps: float = FROZEN_BN_EPS):
+    """FrozenBatchNorm2d in eval as F.batch_norm evaluates it on the CPU (ATen's batch_norm_cpu_inference: invstd = 1 / sqrt(var +
+    eps), alpha = invstd * weight, beta = bias - mean * alpha, all fp32) -> (scale, shift), y = x * scale + shift."""
+    w, b, mean, var = (t.detach().float() for t in (w, b, mean, var))
+    inv = 1.0 / torch.sqrt(var + eps)
+    scale = inv * w
+    return scale, b - mean * scale
+
+
+def regionclip_to_engine(sd: Dict[str, torch.Tensor], pos: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """RegionCLIP / CLIP ResNet state dict -> the engine's ``rn.*`` keys: convolutions rounded to fp16 values (_fp16_values), every FrozenBN as a
+    ``.scale`` / ``.shift`` pair (frozen_bn_affine), the attnpool's q | k | v concatenated along the rows (the in_proj of
+    F.multi_head_attention_forward, clip_backbone.py:87-102).  ``pos`` replaces the attnpool position table (quirk 1, model.py)."""
+    v = _rn_strip(sd)
+    out: Dict[str, torch.Tensor] = {}
+    bn_names = {k[:-len(".running_var")] for k in v if k.endswith(".running_var")}
+    for k, t in v.items():
+        if k.startswith("attnpool."):
+            continue
+        base = k.rsplit(".", 1)[0]
+        if base in bn_names:
+            continue
+        if k.endswith(".weight"):
+            out["rn." + k] = _fp16_values(t)
+    for base in bn_names:
+        sc, sh = frozen_bn_affine(v[base + ".weight"], v[base + ".bias"], v[base + ".running_mean"], v[base + ".running_var"])
+        out["rn.%s.scale" % base], out["rn.%s.shift" % base] = sc, sh
+    a = "attnpool."
+    out["rn.attnpool.positional_embedding"] = (v[a + "positional_embedding"] if pos is None else pos).detach().float()
+    out["rn.attnpool.qkv.weight"] = _fp16_values(torch.cat([v[a + x + "_proj.weight"] for x in "qkv"], 0))
+    out["rn.attnpool.qkv.bias"] = _fp16_values(torch.cat([v[a + x + "_proj.bias"] for x in "qkv"], 0))
+    out["rn.attnpool.c_proj.weight"] = _fp16_values(v[a + "c_proj.weight"])
+    out["rn.attnpool.c_proj.bias"] = _fp16_values(v[a + "c_proj.bias"])
+    return out
+
+
+def _fp16_values(t: torch.Tensor) -> torch.Tensor:
+    """fp32 tensor holding the fp16 values the reference computes with: loader.py always runs convert_weights
+    (clip_backbone.py:578-599), which turns every Conv2d / Linear weight and bias to fp16 before the checkpoint is loaded into
+    them -- so a checkpoint's fp32 values are rounded, in the fp32 parity mode too.  FrozenBN buffers and the attnpool's position
+    table are not converted (they stay fp32)."""
+    return t.detach().float().half().float()
+
+
+def synth_regionclip_rn(seed: int, name: str = "RN50", layers=None, image_resolution: int = 224,
+                        prefix: str = "visual.") -> Dict[str, torch.Tensor]:
+    """Seeded ModifiedResNet weights under ``prefix`` (``visual.`` = a CLIP dict, ``backbone.`` = a RegionCLIP checkpoint's):
+    conv / Linear weights with fp16 values (loader.py always runs convert_weights), fp32 FrozenBN buffers with realistic
+    statistics, bn3 weights nonzero but small so that every residual branch counts and fp16 activations stay O(1) through all
+    blocks; ``layers`` overrides the unit counts (reduced depth for fast tests).  The attnpool table has
+    (image_resolution / 32)^2 + 1 rows; ``text_projection`` [*, output width] is included (loader.py:207)."""
+    arch_layers, width, embed, heads, out_dim = regionclip_arch(name)
+    layers = tuple(layers) if layers is not None else arch_layers
+    g = torch.Generator().manual_seed(seed)
+    w: Dict[str, torch.Tensor] = {}
+
+    def conv(key, cout, cin, k):
+        w[prefix + key] = (torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5).half().float()
+
+    def bn(key, c, gain=(0.6, 1.2)):
+        w[prefix + key + ".weight"] = gain[0] + (gain[1] - gain[0]) * torch.rand(c, generator=g)
+        w[prefix + key + ".bias"] = 0.1 * torch.randn(c, generator=g)
+        w[prefix + key + ".running_mean"] = 0.1 * torch.randn(c, generator=g)
+        w[prefix + key + ".running_var"] = 0.5 + torch.rand(c, generator=g)
+
+    conv("conv1.weight", width // 2, 3, 3); bn("bn1", width // 2)
+    conv("conv2.weight", width // 2, width // 2, 3); bn("bn2", width // 2)
+    conv("conv3.weight", width, width // 2, 3); bn("bn3", width)
+    inplanes = width
+    for L in range(4):
+        planes = width << L
+        for i in range(layers[L]):
+            p = "layer%d.%d." % (L + 1, i)
+            conv(p + "conv1.weight", planes, inplanes, 1); bn(p + "bn1", planes)
+            conv(p + "conv2.weight", planes, planes, 3); bn(p + "bn2", planes)
+            conv(p + "conv3.weight", 4 * planes, planes, 1); bn(p + "bn3", 4 * planes, gain=(0.15, 0.35))
+            if i == 0:
+                conv(p + "downsample.0.weight", 4 * planes, inplanes, 1); bn(p + "downsample.1", 4 * planes, gain=(0.5, 1.0))
+            inplanes = 4 * planes
+    s = image_resolution // 32
+    a = prefix + "attnpool."
+    w[a + "positional_embedding"] = torch.randn(s * s + 1, embed, generator=g) / embed ** 0.5
+    for x in "qkv":
+        w[a + x + "_proj.weight"] = (torch.randn(embed, embed, generator=g) * embed ** -0.5).half().float()
+        w[a + x + "_proj.bias"] = (0.02 * torch.randn(embed, generator=g)).half().float()
+    w[a + "c_proj.weight"] = (torch.randn(out_dim, embed, generator=g) * embed ** -0.5).half().float()
+    w[a + "c_proj.bias"] = (0.02 * torch.randn(out_dim, generator=g)).half().float()
+    w["text_projection"] = torch.zeros(8, out_dim)
+    return w
