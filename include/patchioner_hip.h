@@ -91,6 +91,11 @@ typedef struct {
   int32_t rn_layers[4];       /* Bottleneck units per stage: (3, 4, 6, 3) RN50, (4, 6, 10, 6) RN50x4 */
   int32_t rn_width;           /* stem width: 64 RN50, 80 RN50x4 */
   int32_t rn_attnpool_spatial; /* 1: patch rows = attnpool rows 1.. (use_attnpool_for_spatial_feats); 0: c_proj(x5) without attention */
+  /* vit_arch 1 only (zero otherwise): the LAST vit_self_only_layers blocks attend to themselves only -- INViTE's extract_last_k_th_token
+   * (P/src/INViTE/clipfolder/model.py:216-228: an attention mask that is -inf off the diagonal, so every softmax row is exactly 1 on
+   * itself).  Such a block is x += proj(W_v ln_1(x) + b_v) followed by the MLP: the V third of in_proj is the only part of the fused
+   * projection it multiplies, and no attention kernel runs.  0 <= value <= depth. */
+  int32_t vit_self_only_layers;
 } pio_config;
 
 const char* pio_last_error(void);
@@ -421,7 +426,8 @@ enum {
   PIO_GEMM_EPI_PATCH_EMBED = 0,  /* x[b*Tp + G + p][n] = acc + bias[n] + pos[1 + p][n]      (fp32; p = m mod n2, b = m / n2) */
   PIO_GEMM_EPI_QKV = 1,          /* q, k [B][H][Tk][64], vT [B][H][64][Tk] (operand type; rows m = b*Tp + t) (+ qkv_last [B][T][3D] fp32) */
   PIO_GEMM_EPI_RESIDUAL = 2,     /* x[m][n] = old x joined into the sum + bias[n]                 (fp32, in place) */
-  PIO_GEMM_EPI_GELU = 3          /* out16[m][n] = GELU(acc + bias[n]): act 0 exact erf, 1 QuickGELU (operand type) */
+  PIO_GEMM_EPI_GELU = 3,         /* out16[m][n] = GELU(acc + bias[n]): act 0 exact erf, 1 QuickGELU (operand type) */
+  PIO_GEMM_EPI_BIAS = 4          /* out16[m][n] = acc + bias[n], plain rows (operand type): pio_test_vit_vonly only (WIDE128 and K256) */
 };
 enum {
   PIO_GEMM_PATH_AUTO = 0,        /* what the forward passes take (the dispatch by tile count) */
@@ -449,6 +455,12 @@ typedef struct {
 int pio_test_vit_gemm(int32_t operand, int32_t epi, int32_t path, const pio_test_gemm_args* args, int32_t* path_taken, pio_stream stream);
 /* host only: the PIO_GEMM_PATH_* PIO_GEMM_PATH_AUTO takes for these sizes, PIO_ERR_INVALID_ARG where no kernel takes them */
 int pio_test_gemm_route(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t D, int32_t Tp, int32_t has_capture);
+/* The V-only projection of a self-only block (pio_config.vit_self_only_layers) on its own: out16 [M][D] = A [M][D] . Wv^T + bv in the
+ * operand type, where Wv / bv are rows [2D, 3D) of the FUSED in_proj the caller hands over (in_proj_w [3D][D] operand type, in_proj_b
+ * [3D] fp32) -- the hook slices them as the engine does at load; the q and k thirds are never read.  path: PIO_GEMM_PATH_AUTO,
+ * _WIDE128 or _K256 (the others have no such epilogue and are refused); D % 256 == 0. */
+int pio_test_vit_vonly(int32_t operand, int32_t path, const void* A, const void* in_proj_w, const float* in_proj_b, void* out16, int32_t M,
+                       int32_t D, int32_t* path_taken, pio_stream stream);
 /* kind 0: the ViT flash attention (lens: optional DEVICE [B], 1 <= lens[b] <= T: keys >= lens[b] masked); kind 1: the text tower's
  * causal attention (keys <= query; T, lens unused).  q, k [B][H][Tk][64], vT [B][H][64][Tk] -> out [B*Tp][D], operand type. */
 int pio_test_attention(int32_t kind, int32_t operand, const void* q, const void* k, const void* vT, void* out, int32_t B, int32_t H,

@@ -36,6 +36,7 @@ class PioConfig(ctypes.Structure):
         ("vit_operand_type", c_int32), ("device", c_int32),
         ("vit_arch", c_int32), ("vit_out_dim", c_int32),
         ("rn_layers", c_int32 * 4), ("rn_width", c_int32), ("rn_attnpool_spatial", c_int32),
+        ("vit_self_only_layers", c_int32),
     ]
 
 
@@ -128,6 +129,7 @@ SIGNATURES = {
     "pio_host_pil_table": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "pio_test_vit_gemm": (c_int32, [c_int32, c_int32, c_int32, POINTER(PioTestGemmArgs), POINTER(c_int32), c_void_p]),
     "pio_test_gemm_route": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "pio_test_vit_vonly": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(c_int32), c_void_p]),
     "pio_test_attention": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                      c_int32, c_int32, c_float, c_void_p, c_void_p]),
     "pio_test_layernorm": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_int32,

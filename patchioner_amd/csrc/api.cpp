@@ -72,6 +72,9 @@ struct VitLayerDev {
   float *n1w, *n1b, *qkvb, *projb, *ls1, *n2w, *n2b, *fc1b, *fc2b, *ls2;
   float *projb_ls, *fc2b_ls;     // ls1 * proj.bias, ls2 * fc2.bias: the MFMA path's residual GEMMs take LayerScale folded into their operands
   void *qkvw, *projw, *fc1w, *fc2w;     // projw / fc2w: rows scaled by ls1 / ls2 before the conversion to the operand type (kernels.h, EPI_RESIDUAL)
+  // the V third of the fused in_proj, rows [2D, 3D) of qkvw / qkvb (views, nothing copied): all a self-only block multiplies
+  // (pio_config.vit_self_only_layers)
+  const void* vw; const float* vb;
 };
 
 struct GraphKey {
@@ -390,6 +393,8 @@ int finalize_vit(pio_context* c) {
       if ((rc = upload_op(c, wf.data(), w.rows, w.cols, w.cols, w.dst))) return rc;
       if ((rc = upload_f32(c, bf.data(), w.rows, w.dst == &L.projw ? &L.projb_ls : &L.fc2b_ls))) return rc;
     }
+    L.vw = (const char*)L.qkvw + (size_t)2 * D * D * 2;
+    L.vb = L.qkvb + 2 * D;
     if (c->vit_f32) {
       if ((int)c->vl32.size() != depth) c->vl32.resize(depth);
       float** d32[] = {&c->vl32[l].qkvw, &c->vl32[l].projw, &c->vl32[l].fc1w, &c->vl32[l].fc2w};
@@ -776,6 +781,8 @@ int pio_create(const pio_config* cfg, pio_handle* out) {
   }
   if (cfg->vit_arch >= 1 && cfg->num_registers != 0)
     return fail(PIO_ERR_INVALID_ARG, "pio_create: the CLIP ViT has no registers");
+  if (cfg->vit_self_only_layers != 0 && (cfg->vit_arch != 1 || cfg->vit_self_only_layers < 0 || cfg->vit_self_only_layers > cfg->depth))
+    return fail(PIO_ERR_INVALID_ARG, "pio_create: vit_self_only_layers needs vit_arch 1 (OpenAI-CLIP ViT) and 0 <= vit_self_only_layers <= depth");
   if (cfg->vit_out_dim < 0 || (cfg->vit_out_dim > 0 && cfg->vit_out_dim % 32 != 0) || (cfg->vit_arch == 0 && cfg->vit_out_dim != 0 && cfg->vit_out_dim != cfg->embed_dim))
     return fail(PIO_ERR_INVALID_ARG, "pio_create: vit_out_dim must be 0, or a multiple of 32 with vit_arch 1, 2 or 3");
   int ndev = 0;
@@ -1018,18 +1025,23 @@ int pio_set_memory_bank_device(pio_handle c, const float* dev_bank, int64_t rows
 
 // The same block in exact fp32 (vit_fp32.hip; parity mode): LN -> qkv -> attention -> proj -> x += ls1 * branch -> LN -> fc1 ->
 // GELU -> fc2 -> x += ls2 * branch.  qkv_last: the fused-QKV output of the T valid rows of every image (the hook's tensor).
-static int run_vit_block_f32(pio_handle c, int l, int B, float* qkv_last, const int32_t* lens, hipStream_t s) {
+// self_only (INViTE's last blocks): the attention output of a row is its own V row, so f_ao = xn W_v^T + b_v and nothing else.
+static int run_vit_block_f32(pio_handle c, int l, int B, float* qkv_last, const int32_t* lens, hipStream_t s, bool self_only = false) {
   const VitLayerDev& L = c->vl[l];
   const pio_context::VitLayerF32& W = c->vl32[l];
   const int D = c->D, M = B * c->Tp;
   const float eps = c->cfg.vit_ln_eps;
   HIP_OK(launch_layernorm_f32(c->x, L.n1w, L.n1b, eps, M, D, c->f_xn, s));
+  if (self_only) {
+    HIP_OK(launch_sgemm_tn(c->f_xn, D, W.qkvw + (size_t)2 * D * D, D, L.vb, 1.f, c->f_ao, D, M, D, D, 0, 0, s));
+  } else {
   HIP_OK(launch_sgemm_tn(c->f_xn, D, W.qkvw, D, L.qkvb, 1.f, c->f_qkv, 3 * D, M, 3 * D, D, 0, 0, s));
   if (qkv_last)
     for (int b = 0; b < B; ++b)
       HIP_OK(hipMemcpyAsync(qkv_last + (size_t)b * c->T * 3 * D, c->f_qkv + (size_t)b * c->Tp * 3 * D, (size_t)c->T * 3 * D * 4,
                             hipMemcpyDeviceToDevice, s));
   HIP_OK(launch_attention_f32(c->f_qkv, B, c->H, c->T, c->Tp, D, 0.125f, lens, c->f_ao, s));
+  }
   HIP_OK(launch_sgemm_tn(c->f_ao, D, W.projw, D, L.projb, 1.f, c->f_xn, D, M, D, D, 0, 0, s));
   HIP_OK(launch_resid_ls_f32(c->x, c->f_xn, L.ls1, (size_t)M * D, D, s));
   HIP_OK(launch_layernorm_f32(c->x, L.n2w, L.n2b, eps, M, D, c->f_xn, s));
@@ -1042,8 +1054,13 @@ static int run_vit_block_f32(pio_handle c, int l, int B, float* qkv_last, const 
 
 // One pre-LN DINOv2 block on the B sequences of c->x (in place): LN1 -> qkv -> attention -> proj (+LayerScale,
 // +residual) -> LN2 -> fc1 + GELU -> fc2 (+LayerScale, +residual).  `at.lens` (optional) = per-sequence token counts.
+// self_only (INViTE's last blocks, P/src/INViTE/clipfolder/model.py:216-228: an attention mask that is -inf off the diagonal makes every
+// row's softmax exactly 1 on itself): qkv + attention are replaced by the V-only projection, one GEMM over rows [2D, 3D) of in_proj
+// whose plain [M][D] output (EPI_BIAS) is the proj GEMM's A operand.  No q, k, score or softmax; next_self_only: what the fc2 GEMM's
+// spare workgroups warm for the next block.
 static int run_vit_block(pio_handle c, const VitLayerDev& L, int B, const GemmArgs& g, const VitAttnArgs& at,
-                         float* qkv_last, hipStream_t s, const VitLayerDev* next = nullptr) {
+                         float* qkv_last, hipStream_t s, const VitLayerDev* next = nullptr, bool self_only = false,
+                         bool next_self_only = false) {
   const int D = c->D, M = B * c->Tp;
   const double Malg = (double)B * c->T;   // algorithmic rows: no pad tokens
   // TIMING ablation, compiled only into diagnostic builds (-DPIO_ABLATIONS; tools/microbench/ln_ablation.sh): PIO_ABL_SKIP_LN=1 leaves
@@ -1057,6 +1074,12 @@ static int run_vit_block(pio_handle c, const VitLayerDev& L, int B, const GemmAr
   if (!skip_ln)
   PROF(c, PIO_PROF_VIT_LN, 0, Malg * D * 6.0, s,
        launch_layernorm(c->op, c->x, L.n1w, L.n1b, c->cfg.vit_ln_eps, M, D, c->xn, nullptr, c->T, c->Tp, s));
+  if (self_only) {
+    GemmArgs a = g;
+    a.A = c->xn; a.lda = D; a.W = L.vw; a.bias = L.vb; a.out16 = c->ao; a.M = M; a.N = D; a.K = D;
+    a.pf = L.projw; a.pf_bytes = D * D * 2;
+    PROF(c, PIO_PROF_VIT_GEMM, 2.0 * Malg * D * D, 0, s, launch_vit_gemm(c->op, EPI_BIAS, a, s));
+  } else {
   {
     GemmArgs a = g;
     a.A = c->xn; a.lda = D; a.W = L.qkvw; a.bias = L.qkvb; a.M = M; a.N = 3 * D; a.K = D;
@@ -1065,6 +1088,7 @@ static int run_vit_block(pio_handle c, const VitLayerDev& L, int B, const GemmAr
     PROF(c, PIO_PROF_VIT_GEMM, 2.0 * Malg * 3.0 * D * D, 0, s, launch_vit_gemm(c->op, EPI_QKV, a, s));
   }
   PROF(c, PIO_PROF_VIT_ATTN, 4.0 * B * (double)c->T * c->T * D, 0, s, launch_vit_attention(c->op, at, s));
+  }
   {
     GemmArgs a = g;
     a.A = c->ao; a.lda = D; a.W = L.projw; a.bias = L.projb_ls; a.M = M; a.N = D; a.K = D;
@@ -1084,7 +1108,8 @@ static int run_vit_block(pio_handle c, const VitLayerDev& L, int B, const GemmAr
   {
     GemmArgs a = g;
     a.A = c->hbuf; a.lda = 4 * D; a.W = L.fc2w; a.bias = L.fc2b_ls; a.M = M; a.N = D; a.K = 4 * D;
-    if (next != nullptr) { a.pf = next->qkvw; a.pf_bytes = 3 * D * D * 2; }
+    if (next != nullptr && next_self_only) { a.pf = next->vw; a.pf_bytes = D * D * 2; }
+    else if (next != nullptr) { a.pf = next->qkvw; a.pf_bytes = 3 * D * D * 2; }
     PROF(c, PIO_PROF_VIT_GEMM, 2.0 * Malg * 4.0 * D * D, 0, s, launch_vit_gemm(c->op, EPI_RESIDUAL, a, s));
   }
   return PIO_OK;
@@ -1107,7 +1132,8 @@ static int vit_forward_impl(pio_handle c, const float* imgs, int32_t B, const in
     HIP_OK(launch_embed_scatter_f32(c->f_emb, c->pos, B, c->n2, c->Tp, c->G, D, c->x, s));
     if (c->cfg.vit_arch >= 1) HIP_OK(launch_layernorm_f32(c->x, c->npre_w, c->npre_b, c->cfg.vit_ln_eps, M, D, c->x, s));
     for (int l = 0; l < c->cfg.depth; ++l) {
-      const int rc = run_vit_block_f32(c, l, B, (l == c->cfg.depth - 1) ? qkv_last : nullptr, nullptr, s);
+      const int rc = run_vit_block_f32(c, l, B, (l == c->cfg.depth - 1) ? qkv_last : nullptr, nullptr, s,
+                                       l >= c->cfg.depth - c->cfg.vit_self_only_layers);
       if (rc != PIO_OK) return rc;
     }
     if (c->vhead_w) {
@@ -1138,9 +1164,10 @@ static int vit_forward_impl(pio_handle c, const float* imgs, int32_t B, const in
   VitAttnArgs at;
   at.q = c->q; at.k = c->k; at.vT = c->vT; at.out = c->ao; at.B = B; at.H = c->H; at.T = c->T; at.Tp = c->Tp;
   at.Tk = c->Tk; at.D = D; at.scale = 0.125f;  // 64^-0.5
-  const int depth = c->cfg.depth;
+  const int depth = c->cfg.depth, first_self = depth - c->cfg.vit_self_only_layers;     // blocks [first_self, depth) attend to themselves only
   for (int l = 0; l < depth; ++l) {
-    const int rc = run_vit_block(c, c->vl[l], B, g, at, (l == depth - 1) ? qkv_last : nullptr, s, l + 1 < depth ? &c->vl[l + 1] : nullptr);
+    const int rc = run_vit_block(c, c->vl[l], B, g, at, (l == depth - 1) ? qkv_last : nullptr, s, l + 1 < depth ? &c->vl[l + 1] : nullptr,
+                                 l >= first_self, l + 1 >= first_self);
     if (rc != PIO_OK) return rc;
   }
   if (c->vhead_w) {

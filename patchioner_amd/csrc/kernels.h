@@ -15,7 +15,8 @@ enum GemmEpilogue {
   EPI_PATCH_EMBED = 0,  // x[b*Tp + G + p][n]  = acc + bias[n] + pos[(1+p)][n]          (fp32)
   EPI_QKV = 1,          // q/k [b][h][Tk][64], vT [b][h][64][Tk] (operand type) (+ fp32 qkv_last [B][T][3D])
   EPI_RESIDUAL = 2,     // x[m][n] += acc + bias[n], LayerScale folded into W and bias at load (fp32; the order of the sum: resid_join_ktile)
-  EPI_GELU = 3          // out16[m][n] = gelu_erf(acc + bias[n])                         (operand type)
+  EPI_GELU = 3,         // out16[m][n] = gelu_erf(acc + bias[n])                         (operand type)
+  EPI_BIAS = 4          // out16[m][n] = acc + bias[n], row-major, no activation         (operand type): the V-only projection of a self-only block
 };
 
 #ifndef PIO_GEMM_WARM_NEXT      // extra workgroups that touch the next GEMM's weights (GemmArgs::pf); 0: never launched
@@ -29,7 +30,7 @@ struct GemmArgs {
   // epilogue operands
   float* x;            // residual stream [B*Tp][D] fp32 (PATCH_EMBED, RESIDUAL)
   const float* pos;    // interpolated position table [1+n2][D] (PATCH_EMBED)
-  void* out16;         // GELU output [M][N]
+  void* out16;         // GELU / BIAS output [M][N]
   void* q; void* k; void* vT;   // QKV outputs
   float* qkv_last;     // optional fp32 capture [B][T][3D]
   int T, Tp, Tk, G, n2, D, H;  // tokens / padded rows per image / padded key count / global tokens / patches
@@ -72,7 +73,7 @@ __host__ __device__ constexpr int resid_join_ktile(int e, int nk) { return e + 1
 hipError_t launch_vit_gemm(OperandType t, GemmEpilogue epi, const GemmArgs& a, hipStream_t s);
 // The kernels launch_vit_gemm chooses between (values = PIO_GEMM_PATH_* of the C ABI's test hooks):  NARROW = k_vit_gemm with 64-row
 // tiles (patch embed, proj / fc2), RES128 = its 128-row two-buffer residual form (lazy x join), WIDE128 = its 128-row form of qkv / fc1,
-// K256 = k_vit_gemm256, ROLL = k_vit_gemm_roll.  launch_vit_gemm == launch_vit_gemm_path(route_vit_gemm(epi, a)); route_vit_gemm is
+// K256 = k_vit_gemm256, ROLL = k_vit_gemm_roll.  EPI_BIAS is pinned to WIDE128 and K256 (route_vit_gemm); ROLL refuses it.  launch_vit_gemm == launch_vit_gemm_path(route_vit_gemm(epi, a)); route_vit_gemm is
 // host only and returns -1 where no kernel takes the GEMM.  An explicit path launches only a kernel instantiated for the epilogue whose
 // preconditions hold, else hipErrorInvalidValue (nothing launched).
 enum GemmPath { GEMM_AUTO = 0, GEMM_NARROW = 1, GEMM_RES128 = 2, GEMM_WIDE128 = 3, GEMM_K256 = 4, GEMM_ROLL = 5 };

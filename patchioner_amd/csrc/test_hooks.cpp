@@ -95,6 +95,29 @@ int pio_test_gemm_route(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ld
   return p;
 }
 
+int pio_test_vit_vonly(int32_t operand, int32_t path, const void* A, const void* in_proj_w, const float* in_proj_b, void* out16, int32_t M,
+                       int32_t D, int32_t* path_taken, pio_stream stream) {
+  if (path_taken) *path_taken = -1;
+  if (operand != 0 && operand != 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_vonly: operand 0 (fp16) or 1 (bf16)");
+  if (!A || !in_proj_w || !in_proj_b || !out16) return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_vonly: null buffer");
+  if (M < 1 || D < 256 || D % 256 != 0) return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_vonly: M >= 1, D a multiple of 256");
+  if (path != PIO_GEMM_PATH_AUTO && path != PIO_GEMM_PATH_WIDE128 && path != PIO_GEMM_PATH_K256)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_vonly: the V-only epilogue exists on paths 3 (WIDE128) and 4 (K256) only");
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A = A; g.lda = D; g.M = M; g.N = D; g.K = D; g.D = D; g.H = D / 64; g.Tp = 8; g.T = 8; g.Tk = 64;
+  g.W = (const char*)in_proj_w + (size_t)2 * D * D * 2;       // rows [2D, 3D) of the fused weight (two bytes per element)
+  g.bias = in_proj_b + 2 * D;
+  g.out16 = out16;
+  const int p = path == PIO_GEMM_PATH_AUTO ? route_vit_gemm(EPI_BIAS, g) : path;
+  if (p < 0) return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_vonly: no kernel takes these sizes");
+  const hipError_t e = launch_vit_gemm_path(operand == 1 ? OP_BF16 : OP_F16, EPI_BIAS, (GemmPath)p, g, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_vit_vonly: path " + std::to_string(p) + " refuses M " + std::to_string(M) + ", D " + std::to_string(D));
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_vit_vonly: ") + hipGetErrorString(e));
+  if (path_taken) *path_taken = p;
+  return PIO_OK;
+}
+
 int pio_test_attention(int32_t kind, int32_t operand, const void* q, const void* k, const void* vT, void* out, int32_t B, int32_t H,
                        int32_t T, int32_t Tp, int32_t Tk, int32_t D, float scale, const int32_t* lens, pio_stream stream) {
   if (kind != 0 && kind != 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_attention: kind 0 (ViT) or 1 (text, causal)");

@@ -359,6 +359,8 @@ __global__ __launch_bounds__(256, BM >= 256 ? 2 : (NBUF == 1 ? PIO_GEMM_WIDE_OCC
         *(float4*)(g.x + (size_t)(b * g.Tp + g.G + p) * g.D + n) = make_float4(v.x + ps.x, v.y + ps.y, v.z + ps.z, v.w + ps.w);
       } else if constexpr (EPI == EPI_RESIDUAL) {      // the old x joined the sum in the main loop (PIO_JOIN_X)
         *(float4*)(g.x + (size_t)m * g.N + n) = v;
+      } else if constexpr (EPI == EPI_BIAS) {          // plain [M][N] rows: the A operand of the proj GEMM that follows
+        store_half4<T>((T*)g.out16 + (size_t)m * g.N + n, v.x, v.y, v.z, v.w);
       } else if constexpr (EPI == EPI_GELU) {
         if (g.act == 1) store_half4<T>((T*)g.out16 + (size_t)m * g.N + n, quick_gelu(v.x), quick_gelu(v.y), quick_gelu(v.z), quick_gelu(v.w));
         else store_half4<T>((T*)g.out16 + (size_t)m * g.N + n, gelu_erf(v.x), gelu_erf(v.y), gelu_erf(v.z), gelu_erf(v.w));
@@ -460,6 +462,7 @@ static hipError_t launch_typed(GemmEpilogue epi, GemmPath p, const GemmArgs& a, 
         if constexpr (PIO_GEMM_BM_BIG != 0) { if (a.M >= PIO_GEMM_BIG_M) return launch_one<T, EPI_GELU, PIO_GEMM_BM_BIG == 0 ? 128 : PIO_GEMM_BM_BIG, PIO_GEMM_NBUF_BIG>(a, s); }
         return launch_one<T, EPI_GELU, 128, PIO_GEMM_NBUF_WIDE>(a, s);
       }
+      if (epi == EPI_BIAS) return launch_one<T, EPI_BIAS, 128, PIO_GEMM_NBUF_WIDE>(a, s);
       return hipErrorInvalidValue;
     default:
       return hipErrorInvalidValue;
@@ -505,13 +508,16 @@ static int gemm_rres_min_tiles() {
   return v;
 }
 
+// EPI_BIAS (the V-only projection of a self-only block, N = D) is pinned to two kernels: k_vit_gemm256 from its tile threshold on and
+// the 128-row single-buffer form of k_vit_gemm below it.  k_vit_gemm_roll has no instance of it and refuses it (vit_gemm_roll_fits):
+// the persistent kernel pays from ~2.75 tiles per CU on, which an N = D GEMM reaches only past 300 ViT-B images per launch.
 int route_vit_gemm(GemmEpilogue epi, const GemmArgs& a) {
   if (epi == EPI_RESIDUAL) {
     if (gemm_rres_min_tiles() > 0 && a.M > 0 && a.N % 256 == 0 && ceil_div(a.M, 256) * (a.N / 256) >= gemm_rres_min_tiles() &&
         vit_gemm_roll_fits(epi, a))
       return GEMM_ROLL;
   } else
-  if (gemm_roll_min_tiles() > 0 && a.M > 0 && a.N % 256 == 0 && ceil_div(a.M, 256) * (a.N / 256) >= gemm_roll_min_tiles() &&
+  if (epi != EPI_BIAS && gemm_roll_min_tiles() > 0 && a.M > 0 && a.N % 256 == 0 && ceil_div(a.M, 256) * (a.N / 256) >= gemm_roll_min_tiles() &&
       vit_gemm_roll_fits(epi, a))
     return GEMM_ROLL;
   if (gemm256_min_tiles() > 0 && a.M > 0 && a.N % 256 == 0 && gemm256_wanted(epi, a) && vit_gemm256_fits(epi, a))
@@ -520,7 +526,7 @@ int route_vit_gemm(GemmEpilogue epi, const GemmArgs& a) {
   switch (epi) {
     case EPI_PATCH_EMBED: return GEMM_NARROW;
     case EPI_RESIDUAL: return res128_wanted(a) ? GEMM_RES128 : GEMM_NARROW;
-    case EPI_QKV: case EPI_GELU: return GEMM_WIDE128;
+    case EPI_QKV: case EPI_GELU: case EPI_BIAS: return GEMM_WIDE128;
   }
   return -1;
 }

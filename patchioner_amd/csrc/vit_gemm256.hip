@@ -288,7 +288,7 @@ __global__ __launch_bounds__(512, 2) void k_vit_gemm256(const GemmArgs g) {
   }
 
   // token on the lane: acc[i][j][rt][r] = C[m = m0 + 128 i + 64 wr + 32 rt + r31][n = n0 + 128 j + 32 wc + 8 (r >> 2) + 4 h + (r & 3)]
-  constexpr bool HALF_OUT = EPI == EPI_GELU || EPI == EPI_QKV;
+  constexpr bool HALF_OUT = EPI == EPI_GELU || EPI == EPI_QKV || EPI == EPI_BIAS;
   const bool capture = EPI == EPI_QKV && g.qkv_last != nullptr;   // last block: the fp32 qkv the reference's hook takes
   if (HALF_OUT && !capture) {
     // ---- operand-precision outputs: bias (+ GELU) in registers, one [256][256] half image in LDS (512-B rows, the 16-B
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(512, 2) void k_vit_gemm256(const GemmArgs g) {
       const int ml = (tid >> 5) + 16 * it, m = m0 + ml;
       if (m >= g.M) continue;
       const uint4 v = *(const uint4*)(smem + ml * 512 + ((cc ^ (ml & 15)) << 4));
-      if constexpr (EPI == EPI_GELU) {
+      if constexpr (EPI == EPI_GELU || EPI == EPI_BIAS) {
         *(uint4*)((T*)g.out16 + (size_t)m * g.N + n) = v;
       } else {
         G256_SPLIT(ml, b, t);
@@ -437,6 +437,7 @@ static hipError_t launch256_typed(GemmEpilogue epi, const GemmArgs& a, hipStream
     case EPI_QKV: return launch256_one<T, EPI_QKV>(a, s);
     case EPI_RESIDUAL: return hipErrorInvalidValue;      // k_vit_gemm_roll
     case EPI_GELU: return launch256_one<T, EPI_GELU>(a, s);
+    case EPI_BIAS: return launch256_one<T, EPI_BIAS>(a, s);
   }
   return hipErrorInvalidValue;
 }

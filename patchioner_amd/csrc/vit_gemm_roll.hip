@@ -674,7 +674,7 @@ bool vit_gemm_roll_fits(GemmEpilogue epi, const GemmArgs& a) {
     if ((size_t)a.M * a.lda * 2 >= ((size_t)1 << 31) || (size_t)a.N * a.K * 2 >= ((size_t)1 << 31)) return false;
     return (size_t)a.M * a.N * 4 < ((size_t)1 << 31);      // 32-bit byte offsets into x
   }
-  if (epi != EPI_QKV && epi != EPI_GELU) return false;
+  if (epi != EPI_QKV && epi != EPI_GELU) return false;      // EPI_BIAS: no rolling instance (vit_gemm.hip, route_vit_gemm)
   if (epi == EPI_QKV && (a.qkv_last != nullptr || a.D % TN != 0 || a.Tp % 8 != 0 || a.N != 3 * a.D)) return false;
   if (a.M <= 0 || a.N % TN != 0 || a.K % (2 * TK) != 0 || a.K / TK < 4 || a.lda % 8 != 0) return false;
   if ((size_t)a.M * a.lda * 2 >= ((size_t)1 << 31) || (size_t)a.N * a.K * 2 >= ((size_t)1 << 31)) return false;

@@ -28,7 +28,7 @@ class Engine:
                  max_batch: int = 16, max_prefixes: int = 64, max_steps: int = 30, vit_dtype: str = "fp16",
                  device_index: int = 0, readout_heads: int = 16, readout_scale: float = 0.125, vit_arch: str = "dinov2",
                  vit_out_dim: int = 0, vit_ln_eps: float = 1e-6, rn_layers=(0, 0, 0, 0), rn_width: int = 0,
-                 rn_attnpool_spatial: bool = True):
+                 rn_attnpool_spatial: bool = True, vit_self_only_layers: int = 0):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise PioError(-101, "no HIP device visible: the captioning path has no CPU fallback")
@@ -41,7 +41,8 @@ class Engine:
             dec_ln_eps=1e-5, max_batch=max_batch, max_prefixes=max_prefixes, max_steps=max_steps,
             vit_operand_type={"fp16": 0, "bf16": 1, "fp32": 2}[vit_dtype], device=device_index,
             vit_arch={"dinov2": 0, "clip": 1, "alphaclip": 2, "regionclip": 3}[vit_arch], vit_out_dim=vit_out_dim,
-            rn_layers=(ctypes.c_int32 * 4)(*rn_layers), rn_width=rn_width, rn_attnpool_spatial=int(bool(rn_attnpool_spatial)))
+            rn_layers=(ctypes.c_int32 * 4)(*rn_layers), rn_width=rn_width, rn_attnpool_spatial=int(bool(rn_attnpool_spatial)),
+            vit_self_only_layers=int(vit_self_only_layers))
         self.cfg = cfg
         h = ctypes.c_void_p()
         check(self.lib.pio_create(ctypes.byref(cfg), ctypes.byref(h)))

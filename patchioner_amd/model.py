@@ -6,9 +6,9 @@ attributes (``image_transforms``, ``image_transforms_no_crop``, ``resize_dim``, 
 drivers run unchanged.  Everything numerical is a C-ABI call into libpatchioner_hip.so; there is no CPU
 path (constructing the model without a GPU or without the built library raises).
 
-Scope: the DINOv2(+registers) backbone with the DeCap / CapDec decoder head.  The other
-backbones and heads of the reference (ProxyCLIP, RegionCLIP, INViTE, DenseClip, AlphaClip, OpenCLIP, timm
-CLIP, DINO.txt, MeaCap, ClipCap) raise ``NotImplementedError`` at construction.
+Scope: the DINOv2(+registers), timm OpenAI-CLIP, AlphaCLIP, RegionCLIP and INViTE backbones with the
+DeCap / CapDec and ViECap heads.  The other backbones and heads of the reference (ProxyCLIP, DenseClip, OpenCLIP, DINO.txt,
+MeaCap, ClipCap) raise ``NotImplementedError`` or ``ValueError`` at construction.
 
 Build-specific config keys (there is no network on the target, so nothing is fetched from torch.hub / HF):
   dino_weights     path (.pt/.pth state dict) or dict of the DINOv2 backbone weights
@@ -39,7 +39,7 @@ from .engine import Engine
 from .preprocess import make_transforms
 from .tokenizer import ClipDetokenizer
 
-_OUT_OF_SCOPE = ("proxyclip_clipmodel", "invite_config", "denseclip_config", "clipcap_config")
+_OUT_OF_SCOPE = ("proxyclip_clipmodel", "denseclip_config", "clipcap_config")
 
 
 def _load_state_dict(spec):
@@ -127,6 +127,64 @@ def _regionclip_setup(rc: dict, dino_model, crop_dim: int, synthetic_seed, onlin
                 spatial_attn=bool(rc.get('use_attnpool_for_spatial_feats', True)))
 
 
+def _invite_setup(ic: dict, resize_dim: int, crop_dim: int, synthetic_seed) -> dict:
+    """INViTE's CLIP ViT (P/src/model.py:217-229, 264-301, 459-485; INViTE/loader.py; clipfolder/clip.py:94-143, model.py:468-515):
+    checks the config, loads the checkpoint (``checkpoint``: a local file or a state dict, the tower alone or a full CLIP dict; else
+    synthetic weights from synthetic_seed) and returns the engine's weights with the tower's sizes, the name-derived attributes and
+    the number of self-only blocks.  Everything is checked before the device is touched."""
+    if 'name' not in ic:
+        raise KeyError("'name' key is required in config dictionary")               # INViTE/loader.py:44-45
+    name = ic['name']
+    if ic.get('jit', False):
+        raise NotImplementedError("invite_config jit: true loads a TorchScript archive, which has neither extract_last_k_th_token nor "
+                                  "get_all_last; use jit: false")
+    if str(name).startswith('RN'):
+        raise NotImplementedError("invite_config name %r: INViTE's ModifiedResNet towers take no get_all_last argument "
+                                  "(P/src/model.py:821 fails on them); only the ViT towers are implemented" % (name,))
+    if ic.get('viz', False):
+        # ResidualAttentionBlock asks for nn.MultiheadAttentionViz (clipfolder/model.py:178), which torch does not have
+        raise AttributeError("module 'torch.nn' has no attribute 'MultiheadAttentionViz'")
+    # patch_size and embed_dim come from the NAME (model.py:217-229, 291-301), with the reference's defaults for unknown names
+    if 'ViT-B/32' in name:
+        patch_size = 32
+    elif 'ViT-B/16' in name:
+        patch_size = 16
+    elif 'ViT-L/14' in name:
+        patch_size = 14
+    else:
+        print(f"Unknown INViTE model {name}, using default patch size 32")
+        patch_size = 32
+    if 'ViT-L' in name:
+        embed_dim = 768
+    elif 'ViT-B' in name:
+        embed_dim = 512
+    else:
+        print(f"Unknown INViTE model {name}, using default embedding dimension 512")
+        embed_dim = 512
+    sd = _load_state_dict(ic.get('checkpoint', None))
+    if sd is None:
+        if synthetic_seed is None:
+            raise FileNotFoundError("invite_config['checkpoint'] is required (a local CLIP checkpoint or state dict): clip.load(%r) "
+                                    "would download the weights, which needs network this target does not have; or synthetic_seed"
+                                    % (name,))
+        sd = W.synth_invite_vit(synthetic_seed + 1, name)
+    width, layers, heads, tower_patch, out_dim, grid = W.invite_dims(sd)
+    if tower_patch != patch_size:
+        raise ValueError("invite_config name %r gives patch_size %d, the checkpoint's conv1 is %d x %d: the reference would map boxes "
+                         "and traces to a grid the tower does not have" % (name, patch_size, tower_patch, tower_patch))
+    res = ic.get('resolution', None) or tower_patch * grid
+    n = res // tower_patch
+    if crop_dim // tower_patch != n or crop_dim % tower_patch != 0:
+        # clipfolder/model.py:264: the position table is built for `resolution`; the add fails for any other crop
+        raise RuntimeError("The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 1: the %s tower "
+                           "is built for %d x %d inputs (invite_config resolution)" % ((crop_dim // tower_patch) ** 2 + 1, n * n + 1,
+                                                                                        name, res, res))
+    k = int(ic.get('extract_last_k_th_token', -1))
+    return dict(sd=W.invite_to_engine(sd, resolution=res), width=width, layers=layers, heads=heads, patch_size=patch_size,
+                out_dim=out_dim, embed_dim=embed_dim, resolution=res,
+                self_only=0 if k <= 0 else min(k, layers))              # clipfolder/model.py:216-217: k >= layers masks every block
+
+
 class Patchioner(nn.Module):
 
     def __init__(self, decoder_weights, device, prefix_size, linear_talk2dino, support_memory_size, projection_type=None,
@@ -139,8 +197,7 @@ class Patchioner(nn.Module):
                  vit_dtype="fp16", memory_bank_texts=None, clip_text_weights=None, clip_text_dtype="fp16",
                  talk2dino_projection_weights=None, **kwargs):
         super().__init__(**kwargs)
-        given = dict(proxyclip_clipmodel=proxyclip_clipmodel, invite_config=invite_config,
-                     denseclip_config=denseclip_config, clipcap_config=clipcap_config)
+        given = dict(proxyclip_clipmodel=proxyclip_clipmodel, denseclip_config=denseclip_config, clipcap_config=clipcap_config)
         for k in _OUT_OF_SCOPE:
             if given[k] is not None:
                 raise NotImplementedError("%s: backbone/head outside the MI355X hot-path scope (DINOv2 + DeCap/CapDec)" % k)
@@ -153,9 +210,13 @@ class Patchioner(nn.Module):
             raise ValueError("online_texts is empty")
         is_alpha = alphaclip_config is not None
         is_region = regionclip_config is not None
+        is_invite = invite_config is not None and not is_region       # model.py:214-217: regionclip_config is tested first
         alpha_sd = None
         if is_region:
             rn = _regionclip_setup(regionclip_config, dino_model, crop_dim, synthetic_seed, online_texts)
+        if is_invite:
+            iv = _invite_setup(invite_config, resize_dim, crop_dim, synthetic_seed)
+            is_alpha = False                                           # model.py:459, 515: invite_config is tested before alphaclip_config
         if is_alpha:
             # P/src/model.py:515-545 (alphaclip_loader.load_alphaclip): AlphaCLIP's ViT, the OpenAI-CLIP tower with an alpha input
             # channel.  Name, crop and weights are checked here, before anything touches the device.
@@ -178,7 +239,7 @@ class Patchioner(nn.Module):
         # P/src/model.py:339-392: 'dinov2' names load from torch.hub, 'openai' names are the timm OpenAI-CLIP towers of the
         # "DeCap original" configurations (configs/decap_B16*.k.yaml, decap_B32.k.yaml)
         is_clip = dino_model is not None and 'openai' in dino_model and 'dinov2' not in dino_model
-        if is_alpha or is_region:
+        if is_alpha or is_region or is_invite:
             pass
         elif dino_model is None or 'dinotxt' in dino_model or not ('dinov2' in dino_model or is_clip):
             raise ValueError("Unsupported backbone %r: this build implements the DINOv2 ViT-S/B/L-14 family and the timm "
@@ -217,7 +278,7 @@ class Patchioner(nn.Module):
         self.model_name = dino_model
         # RegionCLIP: 5, as the reference's `"reg" in dino_model` makes it for 'regionclip_*' names (model.py:198) -- read only by the
         # attention read-out, which this backbone never reaches; its tokens are 1 cls row + n^2 patches (self._G)
-        self.num_global_tokens = 1 if is_alpha or dino_model is None or "reg" not in dino_model else 5
+        self.num_global_tokens = 1 if is_alpha or is_invite or dino_model is None or "reg" not in dino_model else 5
         self._G = 1 if is_region else self.num_global_tokens
         if is_region:
             # model.py:214-216, 254-263: patch_size and embed_dim come from the config; the tokens are the attnpool's output width
@@ -229,6 +290,10 @@ class Patchioner(nn.Module):
             depth, heads, patch_size, self.token_dim = 0, alpha_heads, alpha_p, alpha_out
             self.embed_dim = alphaclip_config.get('embed_dim', alpha_out)
             self.alphaclip_config = dict(alphaclip_config)
+        elif is_invite:
+            # model.py:217-229, 291-301: patch_size and embed_dim from the model NAME; the tokens are ln_post(x) @ proj wide
+            depth, heads, patch_size, self.token_dim = iv["layers"], iv["heads"], iv["patch_size"], iv["out_dim"]
+            self.embed_dim = iv["embed_dim"]
         elif is_clip:
             # timm VisionTransformer with pre_norm, nn.LayerNorm (eps 1e-5), QuickGELU (model.py:363-371); the reference hands
             # img_size=resize_dim to timm, which resamples the checkpoint's position table for any size but 224 at load
@@ -242,17 +307,21 @@ class Patchioner(nn.Module):
             raise ValueError("crop_dim must be a multiple of %d (the reference's reshape fails otherwise)" % patch_size)
         self.num_patch_tokens = crop_dim // patch_size * crop_dim // patch_size
         self.num_tokens = self.num_global_tokens + self.num_patch_tokens
-        self.num_attn_heads = 16 if is_alpha or is_region or 'vits' not in dino_model else 6
+        self.num_attn_heads = 16 if is_alpha or is_region or is_invite or 'vits' not in dino_model else 6
         self.scale = 0.125
         self.patch_size = patch_size
-        self.backbone_type = 'RegionCLIP' if is_region else ('AlphaClip' if is_alpha else ('CLIP' if is_clip else 'DINO'))  # model.py:634-651
-        if is_clip or is_alpha or is_region:
+        self.backbone_type = 'RegionCLIP' if is_region else ('INViTE' if is_invite else ('AlphaClip' if is_alpha else ('CLIP' if is_clip else 'DINO')))  # model.py:634-651
+        if is_clip or is_alpha or is_region or is_invite:
             from .preprocess import CLIP_MEAN, CLIP_STD
             self.image_transforms, self.image_transforms_no_crop = make_transforms(resize_dim, crop_dim, CLIP_MEAN, CLIP_STD)
+            if is_invite:
+                # model.py:463-473: clip._transform(input_resolution) -- resize AND crop to the tower's resolution, whatever resize_dim
+                # and crop_dim say; the no-crop transform squares to resize_dim
+                self.image_transforms = make_transforms(iv["resolution"], iv["resolution"], CLIP_MEAN, CLIP_STD)[0]
         else:
             self.image_transforms, self.image_transforms_no_crop = make_transforms(resize_dim, crop_dim)
 
-        vit_sd = rn["sd"] if is_region else (alpha_sd if is_alpha else _load_state_dict(dino_weights))
+        vit_sd = rn["sd"] if is_region else (iv["sd"] if is_invite else (alpha_sd if is_alpha else _load_state_dict(dino_weights)))
         if vit_sd is None:
             if synthetic_seed is None:
                 raise FileNotFoundError("dino_weights is required: torch.hub.load('facebookresearch/dinov2', ...) / "
@@ -260,7 +329,7 @@ class Patchioner(nn.Module):
             vit_sd = W.synth_clip_vit(synthetic_seed + 1, dino_model) if is_clip else W.synth_dinov2(synthetic_seed + 1, dino_model)
         if not is_region:
             depth = 1 + max(int(k.split(".")[1]) for k in vit_sd if k.startswith("blocks."))
-        if attention_type != 'qkv' and not is_clip and not is_alpha and not is_region:
+        if attention_type != 'qkv' and not is_clip and not is_alpha and not is_region and not is_invite:
             # the reference re-orders the last block's fused q|k|v rows (P/src/model.py:569-582)
             vit_sd = dict(vit_sd)
             D = self.embed_dim
@@ -304,10 +373,15 @@ class Patchioner(nn.Module):
                            vit_out_dim=rn["out_dim"], vit_ln_eps=1e-5, rn_layers=rn["layers"], rn_width=rn["width"],
                            rn_attnpool_spatial=rn["spatial_attn"])
         else:
-            arch_kw = dict(embed_dim=alpha_dv if is_alpha else self.embed_dim, num_registers=self.num_global_tokens - 1,
+            clip_like = is_clip or is_alpha or is_invite
+            arch_kw = dict(embed_dim=alpha_dv if is_alpha else (iv["width"] if is_invite else self.embed_dim),
+                           num_registers=self.num_global_tokens - 1,
                            pretrain_grid=int(math.isqrt(vit_sd["pos_embed"].shape[1] - 1)),
-                           vit_arch="alphaclip" if is_alpha else ("clip" if is_clip else "dinov2"),
-                           vit_out_dim=self.token_dim if is_clip or is_alpha else 0, vit_ln_eps=1e-5 if is_clip or is_alpha else 1e-6)
+                           vit_arch="alphaclip" if is_alpha else ("clip" if clip_like else "dinov2"),
+                           vit_out_dim=self.token_dim if clip_like else 0, vit_ln_eps=1e-5 if clip_like else 1e-6,
+                           # INViTE: the tower is the CLIP engine whose last blocks attend to themselves only; its table arrives
+                           # at the tower's own grid (weights.invite_to_engine), so the engine resamples nothing
+                           vit_self_only_layers=iv["self_only"] if is_invite else 0)
         self.engine = Engine(depth=depth, num_heads=heads, crop_dim=crop_dim, patch_size=patch_size, prefix_size=prefix_size,
                              max_batch=max_batch, max_prefixes=max_prefixes, vit_dtype=vit_dtype,
                              device_index=self._device.index, readout_heads=self.num_attn_heads, readout_scale=self.scale,

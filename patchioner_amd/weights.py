@@ -187,7 +187,15 @@ def alphaclip_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     ``visual.`` prefix) -> the engine's keys: the timm names of the CLIP tower (cls_token, pos_embed, patch_embed.proj.weight, norm_pre,
     blocks.{i}.*, norm, head.weight = proj^T) plus ``patch_embed.alpha.weight`` for conv1_alpha (zeros when the checkpoint has none,
     alpha_clip/model.py:603-606)."""
-    src = {(k[len("visual."):] if k.startswith("visual.") else k): v for k, v in sd.items()}
+    out = _openai_visual_to_engine({(k[len("visual."):] if k.startswith("visual.") else k): v for k, v in sd.items()})
+    if "patch_embed.alpha.weight" not in out:
+        pw = out["patch_embed.proj.weight"]
+        out["patch_embed.alpha.weight"] = torch.zeros(pw.shape[0], 1, pw.shape[2], pw.shape[3], dtype=pw.dtype)
+    return out
+
+
+def _openai_visual_to_engine(src: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The keys of an OpenAI-layout ``VisionTransformer`` state dict (no ``visual.`` prefix) under the engine's timm names."""
     out: Dict[str, torch.Tensor] = {}
     for k, v in src.items():
         k = k.replace("in_proj_weight", "in_proj.weight").replace("in_proj_bias", "in_proj.bias")
@@ -213,10 +221,121 @@ def alphaclip_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
             out["head.weight"] = v.t().contiguous()
         else:
             raise KeyError("unexpected AlphaCLIP visual key %r" % k)
-    if "patch_embed.alpha.weight" not in out:
-        pw = out["patch_embed.proj.weight"]
-        out["patch_embed.alpha.weight"] = torch.zeros(pw.shape[0], 1, pw.shape[2], pw.shape[3], dtype=pw.dtype)
     return out
+
+
+INVITE_ARCHS = dict(ALPHACLIP_ARCHS, **{"ViT-L/14@336px": ("vit_large_patch14_clip_224", 336)})
+
+
+def invite_arch(name: str):
+    """-> (width, layers, heads, patch, output dim, native resolution) of an INViTE tower name (the ViT names of clip.available_models(),
+    P/src/INViTE/clipfolder/clip.py:30-40).  Unknown names raise RuntimeError like clip.load (:125)."""
+    if name not in INVITE_ARCHS:
+        raise RuntimeError("Model %s not found; available models = %s" % (name, list(INVITE_ARCHS)))
+    timm_name, res = INVITE_ARCHS[name]
+    return clip_arch(timm_name) + (res,)
+
+
+def _cn(g, shape, std):
+    """Clamped normal: the generator's own randn, then clamp and scale, which are exact IEEE operations -- the same bits on every host.
+    (_tn's trunc_normal_ goes through a vectorised erfinv whose last bit differs between CPUs: after a loader that rounds weights to
+    fp16, such a bit moves a tower's fp32 tokens by 1e-5.)"""
+    return torch.randn(shape, generator=g).clamp_(-2.0, 2.0) * std
+
+
+def synth_invite_vit(seed: int, name: str = "ViT-B/16", depth: int | None = None) -> Dict[str, torch.Tensor]:
+    """State dict of the visual tower of an OpenAI CLIP checkpoint, ``visual.`` prefix stripped, as INViTE's build_model reads it
+    (P/src/INViTE/clipfolder/model.py:240-257, 468-515): conv1.weight, class_embedding, positional_embedding, ln_pre,
+    transformer.resblocks.{i}.{ln_1, attn.in_proj_weight, attn.in_proj_bias, attn.out_proj, ln_2, mlp.c_fc, mlp.c_proj}, ln_post,
+    proj [width, output_dim].  fp32 values that are NOT fp16-representable: the loader's rounding (invite_to_engine) is visible.
+    Drawn with _cn, so that the checkpoint is the same bits on every host (a fixture of the reference's fp32 tokens is held to 1e-5)."""
+    D, full_depth, _, p, out, res = invite_arch(name)
+    depth = depth or full_depth
+    n = res // p
+    g = torch.Generator().manual_seed(seed)
+    w: Dict[str, torch.Tensor] = {}
+    w["conv1.weight"] = _cn(g, (D, 3, p, p), 0.02)
+    w["class_embedding"] = _cn(g, (D,), 0.02)
+    w["positional_embedding"] = _cn(g, (1 + n * n, D), 0.02)
+    w["ln_pre.weight"] = 0.5 + torch.rand(D, generator=g)
+    w["ln_pre.bias"] = _cn(g, (D,), 0.02)
+    for i in range(depth):
+        q = "transformer.resblocks.%d." % i
+        for ln in ("ln_1", "ln_2"):
+            w[q + ln + ".weight"] = 0.5 + torch.rand(D, generator=g)
+            w[q + ln + ".bias"] = _cn(g, (D,), 0.02)
+        qkv = _cn(g, (3 * D, D), 0.02)
+        qkv[: 2 * D] *= 2.5
+        w[q + "attn.in_proj_weight"] = qkv
+        w[q + "attn.in_proj_bias"] = _cn(g, (3 * D,), 0.02)
+        w[q + "attn.out_proj.weight"] = _cn(g, (D, D), 0.02) * 0.3
+        w[q + "attn.out_proj.bias"] = _cn(g, (D,), 0.02)
+        w[q + "mlp.c_fc.weight"] = _cn(g, (4 * D, D), 0.02)
+        w[q + "mlp.c_fc.bias"] = _cn(g, (4 * D,), 0.02)
+        w[q + "mlp.c_proj.weight"] = _cn(g, (D, 4 * D), 0.02) * 0.3
+        w[q + "mlp.c_proj.bias"] = _cn(g, (D,), 0.02)
+    w["ln_post.weight"] = 0.5 + torch.rand(D, generator=g)
+    w["ln_post.bias"] = _cn(g, (D,), 0.02)
+    w["proj"] = _cn(g, (D, out), 0.03)
+    return w
+
+
+def invite_visual(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The visual tower of ``sd``: the ``visual.*`` keys of a full CLIP state dict (text tower beside them) without the prefix, or
+    ``sd`` itself when it is the tower alone.  ResNet towers (``visual.layer1...``, no ``proj``) raise NotImplementedError."""
+    vis = {k[len("visual."):]: v for k, v in sd.items() if k.startswith("visual.")} or dict(sd)
+    if "proj" not in vis:
+        raise NotImplementedError("INViTE with a ModifiedResNet tower (no visual.proj in the checkpoint): only the ViT towers carry "
+                                  "extract_last_k_th_token (P/src/INViTE/clipfolder/model.py:536-546)")
+    return vis
+
+
+def invite_dims(sd: Dict[str, torch.Tensor]):
+    """-> (width, layers, heads, patch, output dim, grid of the position table) read from the checkpoint's shapes, as build_model does
+    (P/src/INViTE/clipfolder/model.py:471-477, 536: heads = width // 64)."""
+    vis = invite_visual(sd)
+    width, patch = int(vis["conv1.weight"].shape[0]), int(vis["conv1.weight"].shape[-1])
+    layers = len([k for k in vis if k.endswith(".attn.in_proj_weight") or k.endswith(".attn.in_proj.weight")])
+    grid = round((vis["positional_embedding"].shape[0] - 1) ** 0.5)
+    return width, layers, width // 64, patch, int(vis["proj"].shape[1]), grid
+
+
+def invite_resize_pos_embed(pe: torch.Tensor, grid: int) -> torch.Tensor:
+    """resize_pos_embed (P/src/INViTE/clipfolder/model.py:454-466): the class row kept apart, the grid through
+    F.interpolate(mode='bicubic', align_corners=False) WITHOUT antialias -- not timm's resampler, which the engine applies to a table
+    of another grid (antialias=True).  [1 + g^2, C] -> [1 + grid^2, C], in the table's own dtype."""
+    import torch.nn.functional as F
+    g = int((pe.shape[0] - 1) ** 0.5)
+    patch = pe[1:].reshape(1, g, g, -1).permute(0, 3, 1, 2)
+    patch = F.interpolate(patch, size=(grid, grid), mode="bicubic", align_corners=False)
+    return torch.cat([pe[:1], patch.permute(0, 2, 3, 1).reshape(grid * grid, -1)], dim=0)
+
+
+_INVITE_FP16 = ("conv1.weight", "attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight", "attn.out_proj.bias",
+                "mlp.c_fc.weight", "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias")
+
+
+def invite_to_engine(sd: Dict[str, torch.Tensor], resolution: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """INViTE's loader (build_model, P/src/INViTE/clipfolder/model.py:468-515) -> the engine's CLIP keys (``vit_arch = 1``):
+
+    * convert_weights (:425-449) makes the Conv2d / Linear / MultiheadAttention weights and biases and ``proj`` fp16 parameters, so
+      load_state_dict rounds exactly those tensors to fp16 VALUES; class_embedding, positional_embedding and the LayerNorms stay fp32;
+    * with ``resolution`` of another grid than the checkpoint's, the position table is resampled by resize_pos_embed (:454-466,
+      510-512).  Done here, so that the engine gets a table at its own grid (pretrain_grid = the new grid) and its timm-style
+      resampler stays out of it.
+
+    Accepts the tower alone or a full CLIP state dict (``visual.`` prefix beside the text tower's keys)."""
+    vis = invite_visual(sd)
+    _, _, _, patch, _, grid = invite_dims(vis)
+    src: Dict[str, torch.Tensor] = {}
+    for k, v in vis.items():
+        v = v.detach()
+        if k == "proj" or k.endswith(_INVITE_FP16):
+            v = v.half()
+        src[k] = v.float()
+    if resolution is not None and resolution // patch != grid:
+        src["positional_embedding"] = invite_resize_pos_embed(vis["positional_embedding"].detach(), resolution // patch).float()
+    return _openai_visual_to_engine(src)
 
 
 def add_outlier_channels(w: Dict[str, torch.Tensor], channels=(7, 300, 611), block: int = 1, gain: float = 4000.0,
