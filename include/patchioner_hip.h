@@ -326,6 +326,33 @@ int pio_viecap_build_prompt_ragged(pio_handle h, const float* cont_dev, const in
 int pio_lm_beam_search(pio_handle h, const float* embeds_dev, const int32_t* plen_dev, int32_t N, int32_t Pmax, int32_t W, int32_t steps,
                        int32_t eos0, int32_t eos1, int32_t* ids_dev, int32_t* lens_dev, float* scores_dev, pio_stream stream);
 
+/* -- ClipCap head (P/src/clipcap/entrypoint.py): the MLP prefix mapper, top-p (nucleus) sampling, the sampling decode loop.
+ * The checkpoint arrives through pio_load_weight under its own names: clip_project.model.0.* [H, C] and clip_project.model.2.*
+ * [Lp * 768, H] (MLP: Linear, Tanh, Linear; C in {384, 512, 640, 768, 1024}, H a multiple of 768) and gpt.* as for the ViECap head.
+ *   pio_clipcap_mapping: feats_dev [N, C] -> out_dev [N, Lp, 768]; normalize != 0: the rows are L2-normalised first, on a copy
+ *     (feats_dev is not written).  N <= min(max_prefixes, 128).  pio_clipcap_prefix_length: Lp (0 without a mapper).
+ *   pio_nucleus_sample: one token per row of scores_dev [N, V] fp32 (V = the handle's vocabulary; raw logits or log-probabilities,
+ *     a per-row constant is immaterial).  p = softmax(scores / temperature) (temperature <= 0: 1); the kept set is the reference's
+ *     shifted top-p mask -- the largest token always, token i iff the probability mass of the tokens ABOVE it is <= top_p; every token
+ *     tied with the edge is kept -- and the token is the smallest kept id whose kept-mass prefix sum in ascending id order exceeds
+ *     uniforms_dev[n] x (kept mass), uniforms in [0, 1).  active_dev [N] int32 in / out: a row whose flag is 0 emits stop_id and stays 0;
+ *     a row that draws stop_id turns 0; a row with a NaN (or an inf) emits stop_id.  tokens_dev [N] int32; kept_dev [N] int32 or NULL:
+ *     the kept-set sizes (0 for rows that did not sample).  The result of a row does not depend on where it sits in the launch.
+ *   pio_lm_sample: embeds_dev [N, P, 768] prefilled once, then `steps` rounds of sample and advance, enqueue-only and graph-captured
+ *     (keyed on N, P, steps, temperature, top_p, stop_id); every flag lives on the device and nothing waits for it; works on decoder
+ *     clones.  uniforms_dev [N, steps] or NULL: then u[n][k] is Philox4x32-10 with key = seed and counter (n, k, 0, 0), first output
+ *     word >> 8 times 2^-24 (pio_host_philox_uniform is the same function on the host).  ids_dev [N, steps] int32 (stop_id from a row's
+ *     first stop on); lens_dev [N] int32 = index of the first stop token + 1, or steps.  All `steps` rounds run.
+ *     A call counts its rows from 0: a caller that splits a batch over several calls and wants the ids of the unsplit batch passes
+ *     uniforms_dev filled by pio_host_philox_uniforms(seed, first row of the call, ...).
+ *     Bounds: N <= min(max_prefixes, 128), P + steps - 1 <= max_steps (PIO_ERR_CAPACITY); otherwise PIO_ERR_INVALID_ARG. */
+int pio_clipcap_mapping(pio_handle h, const float* feats_dev, int32_t N, int32_t normalize, float* out_dev, pio_stream stream);
+int pio_clipcap_prefix_length(pio_handle h);
+int pio_nucleus_sample(pio_handle h, const float* scores_dev, int32_t N, float temperature, float top_p, const float* uniforms_dev,
+                       int32_t stop_id, int32_t* active_dev, int32_t* tokens_dev, int32_t* kept_dev, pio_stream stream);
+int pio_lm_sample(pio_handle h, const float* embeds_dev, int32_t N, int32_t P, int32_t steps, float temperature, float top_p,
+                  int32_t stop_id, uint64_t seed, const float* uniforms_dev, int32_t* ids_dev, int32_t* lens_dev, pio_stream stream);
+
 /* -- measurement: live HIP-event timing of the launches a call makes, on the stream they are launched on.
  *    While enabled every bracketed launch records a (start, stop) event pair; pio_profile_read waits for the
  *    recorded events of one class and returns the summed device time, the launch count and the ALGORITHMIC
@@ -417,6 +444,13 @@ int pio_host_interpolate_pos_embed_plain(const float* pos, int32_t grid, int32_t
  * count * pio_host_pil_ksize(in_size, out_size) int32, bounds 2 * count (min, taps). */
 int pio_host_pil_ksize(int32_t in_size, int32_t out_size);
 int pio_host_pil_table(int32_t in_size, int32_t out_size, int32_t first, int32_t count, int32_t* kk, int32_t* bounds);
+/* The sampler's counter-based generator on the host (no device): Philox4x32-10, out[4] from counter ctr[4] and the 64-bit key
+ * (key_lo, key_hi); and the uniform pio_lm_sample draws for (row, step) under `seed` -- the fp32 value k / 2^24, written to *u. */
+int pio_host_philox4x32(const uint32_t* ctr, uint32_t key_lo, uint32_t key_hi, uint32_t* out);
+int pio_host_philox_uniform(uint64_t seed, uint32_t row, uint32_t step, float* u);
+/* out[n * steps + k] = the uniform of (row0 + n, k) under `seed`, n < N, k < steps: what pio_lm_sample draws for a call whose first row
+ * is row `row0` of a larger batch, for callers that split a batch over several calls and pass uniforms_dev. */
+int pio_host_philox_uniforms(uint64_t seed, uint32_t row0, int32_t N, int32_t steps, float* out);
 
 /* ---- Test hooks: the ViT block kernels one at a time, for the kernel-by-kernel tests.  Caller-owned DEVICE pointers (torch
  *      tensors' data_ptr()), the current HIP device, no pio_handle.  Every size is validated before anything is launched; a refused
@@ -489,6 +523,10 @@ int pio_test_avgpool(int32_t operand, const void* x, int32_t B, int32_t H, int32
  * rows 1..HW = x + pos[1..], zero rows to Tp */
 int pio_test_attnpool_in(int32_t operand, const void* x, const float* pos, int32_t B, int32_t HW, int32_t C, int32_t Tp, void* out,
                          pio_stream stream);
+
+/* k_nucleus_sample at any V, without a handle: pio_nucleus_sample's arguments with scores [N, V]. */
+int pio_test_nucleus_sample(const float* scores, int32_t N, int32_t V, float temperature, float top_p, const float* uniforms, int32_t stop_id,
+                            int32_t* active, int32_t* tokens, int32_t* kept, pio_stream stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -102,6 +102,11 @@ SIGNATURES = {
                                                  c_void_p]),
     "pio_lm_beam_search": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
+    "pio_clipcap_mapping": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "pio_clipcap_prefix_length": (c_int32, [c_void_p]),
+    "pio_nucleus_sample": (c_int32, [c_void_p, c_void_p, c_int32, c_float, c_float, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pio_lm_sample": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_int32, c_uint64, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
     "pio_mem_topk": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "pio_text_project": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                                    c_void_p, c_void_p, c_void_p]),
@@ -127,6 +132,9 @@ SIGNATURES = {
     "pio_host_interpolate_pos_embed_plain": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_double, c_void_p]),
     "pio_host_pil_ksize": (c_int32, [c_int32, c_int32]),
     "pio_host_pil_table": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "pio_host_philox4x32": (c_int32, [POINTER(c_uint32), c_uint32, c_uint32, POINTER(c_uint32)]),
+    "pio_host_philox_uniform": (c_int32, [c_uint64, c_uint32, c_uint32, POINTER(c_float)]),
+    "pio_host_philox_uniforms": (c_int32, [c_uint64, c_uint32, c_int32, c_int32, c_void_p]),
     "pio_test_vit_gemm": (c_int32, [c_int32, c_int32, c_int32, POINTER(PioTestGemmArgs), POINTER(c_int32), c_void_p]),
     "pio_test_gemm_route": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     "pio_test_vit_vonly": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(c_int32), c_void_p]),
@@ -139,6 +147,8 @@ SIGNATURES = {
                                 c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "pio_test_avgpool": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "pio_test_attnpool_in": (c_int32, [c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "pio_test_nucleus_sample": (c_int32, [c_void_p, c_int32, c_int32, c_float, c_float, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -171,6 +171,12 @@ struct pio_context {
   std::vector<ViecapMapLayerW> ml;
   float *map_lin = nullptr, *map_x = nullptr, *map_ln = nullptr, *map_q = nullptr, *map_kv = nullptr, *map_att = nullptr, *map_hid = nullptr;
   float* ent = nullptr; int ent_K = 0;            // [K][C] L2-normalised entity text embeddings
+  // ClipCap head: the MLP prefix mapper's weights (nn.Linear layouts) and workspaces; sampling state of pio_lm_sample (allocated on first use)
+  bool has_ccmap = false;
+  int cc_C = 0, cc_H = 0, cc_Nout = 0;
+  float *cc_w1 = nullptr, *cc_b1 = nullptr, *cc_w2 = nullptr, *cc_b2 = nullptr, *cc_zeros = nullptr, *cc_x = nullptr, *cc_hid = nullptr;
+  float* smp_u = nullptr;                         // [rows][max_steps] uniforms
+  int32_t* smp_i = nullptr;                       // active [rows], lens [rows]
   float* prompt_buf = nullptr;                    // [max_prefixes][max_steps][E]
   float *pre_x = nullptr, *pre_qkv = nullptr, *pre_att = nullptr, *pre_hid = nullptr;   // batched prompt prefill (decoder.hip), kPrefillRows rows
   static constexpr int kPrefillRows = 2048;
@@ -471,7 +477,9 @@ int finalize_decoder(pio_context* c) {
   if (E != 768) return fail(PIO_ERR_SHAPE, "decoder kernels are built for n_embd = 768 (the DeCap GPT-2 config)");
   const HostTensor *t, *tw, *tb, *tl, *tlb;
   int rc;
-  if (find(c, "clip_project.model.0.weight")) {        // DeCap's prefix projection; a ViECap language model has none
+  // DeCap's prefix projection; a ViECap language model has none, and a ClipCap checkpoint's clip_project is its MLP mapper (model.0 and
+  // model.2: finalize_clipcap_map)
+  if (find(c, "clip_project.model.0.weight") && !find(c, "clip_project.model.2.weight")) {
     if ((rc = need(c, "clip_project.model.0.weight", {E, PS}, &t))) return rc;
     if ((rc = upload_f32(c, t->data.data(), (size_t)E * PS, &c->clip_w))) return rc;
     if ((rc = need(c, "clip_project.model.0.bias", {E}, &t))) return rc;
@@ -655,6 +663,34 @@ int finalize_viecap_map(pio_context* c) {
   return PIO_OK;
 }
 
+// ClipCap's default mapper, MLP((C, Lp E / 2, Lp E)) = clip_project.model.0 (Linear), Tanh, clip_project.model.2 (Linear)
+// (P/src/clipcap/entrypoint.py:20-31, 179-181)
+int finalize_clipcap_map(pio_context* c) {
+  const int E = c->cfg.dec_embd;
+  const HostTensor* w1 = find(c, "clip_project.model.0.weight");
+  const HostTensor* w2 = find(c, "clip_project.model.2.weight");
+  if (!w1 || !w2 || w1->shape.size() != 2 || w2->shape.size() != 2 || w2->shape[1] != w1->shape[0])
+    return fail(PIO_ERR_SHAPE, "clip_project.model.0.weight [H, C] / clip_project.model.2.weight [Lp*E, H] missing or mis-shaped");
+  const int C = (int)w1->shape[1], H = (int)w1->shape[0], Nout = (int)w2->shape[0];
+  if (!(C == 384 || C == 512 || C == 640 || C == 768 || C == 1024) || H % 768 != 0 || Nout % E != 0 || Nout / E > 64)
+    return fail(PIO_ERR_SHAPE, "ClipCap MLP mapper: C must be 384, 512, 640, 768 or 1024, the hidden width a multiple of 768, the output Lp x n_embd");
+  const HostTensor* t;
+  int rc;
+  if ((rc = upload_f32(c, w1->data.data(), w1->data.size(), &c->cc_w1))) return rc;
+  if ((rc = need(c, "clip_project.model.0.bias", {H}, &t))) return rc;
+  if ((rc = upload_f32(c, t->data.data(), H, &c->cc_b1))) return rc;
+  if ((rc = upload_f32(c, w2->data.data(), w2->data.size(), &c->cc_w2))) return rc;
+  if ((rc = need(c, "clip_project.model.2.bias", {Nout}, &t))) return rc;
+  if ((rc = upload_f32(c, t->data.data(), Nout, &c->cc_b2))) return rc;
+  const size_t N = c->cfg.max_prefixes < 128 ? c->cfg.max_prefixes : 128;
+  if ((rc = c->dmalloc(&c->cc_zeros, (size_t)Nout, true))) return rc;
+  if ((rc = c->dmalloc(&c->cc_x, N * C, true))) return rc;
+  if ((rc = c->dmalloc(&c->cc_hid, N * H, true))) return rc;
+  c->cc_C = C; c->cc_H = H; c->cc_Nout = Nout;
+  c->has_ccmap = true;
+  return PIO_OK;
+}
+
 bool is_ignorable_key(const std::string& k) {
   auto ends = [&](const char* s) { size_t n = strlen(s); return k.size() >= n && k.compare(k.size() - n, n, s) == 0; };
   return k == "mask_token" || k == "decoder.lm_head.weight" || ends(".attn.bias") || ends(".attn.masked_bias");
@@ -665,7 +701,7 @@ bool is_known_key(const std::string& k) {
                                 "patch_embed.proj.bias", "patch_embed.alpha.weight", "norm.weight", "norm.bias", "norm_pre.weight", "norm_pre.bias", "head.weight", "talk2dino.A_pinv",
                                 "talk2dino.b"};
   for (auto e : exact) if (k == e) return true;
-  return k.rfind("blocks.", 0) == 0 || k.rfind("decoder.transformer.", 0) == 0 || k.rfind("clip_project.model.0.", 0) == 0 ||
+  return k.rfind("blocks.", 0) == 0 || k.rfind("decoder.transformer.", 0) == 0 || k.rfind("clip_project.model.0.", 0) == 0 || k.rfind("clip_project.model.2.", 0) == 0 ||
          k.rfind("mapping_network.", 0) == 0 || k.rfind("rn.", 0) == 0;
 }
 
@@ -925,6 +961,9 @@ int pio_finalize_weights(pio_handle c) {
   }
   if (find(c, "mapping_network.linear.weight")) {
     if ((rc = finalize_viecap_map(c))) return rc;
+  }
+  if (find(c, "clip_project.model.2.weight")) {
+    if ((rc = finalize_clipcap_map(c))) return rc;
   }
   if (find(c, "talk2dino.A_pinv")) {
     const HostTensor* t;
@@ -1803,6 +1842,94 @@ int pio_lm_beam_search(pio_handle c, const float* embeds, const int32_t* plen, i
   return PIO_OK;
 }
 
+// The sampler and the sampling loop are referenced weakly for the same reason as the launchers above (sample.hip, decoder.hip).
+extern "C++" {
+namespace pio {
+hipError_t launch_nucleus_sample(const SampleArgs& a, hipStream_t s) __attribute__((weak));
+hipError_t launch_philox_uniforms(uint64_t seed, int N, int steps, float* u, hipStream_t s) __attribute__((weak));
+hipError_t launch_lm_sample(const DecoderArgs& a, const float* prompt, int P, float temperature, float top_p, int stop_id,
+                            const float* uniforms, int32_t* active, float* stats, int32_t* lens, hipStream_t s) __attribute__((weak));
+hipError_t launch_clipcap_mapping(const float* x, int N, int C, int H, int Nout, const float* w1, const float* b1, const float* w2,
+                                  const float* b2, const float* zeros, float* hid, float* out, hipStream_t s) __attribute__((weak));
+}  // namespace pio
+}  // extern "C++"
+
+int pio_clipcap_mapping(pio_handle c, const float* feats, int32_t N, int32_t normalize, float* out, pio_stream stream) {
+  if (!c || !feats || !out) return fail(PIO_ERR_INVALID_ARG, "pio_clipcap_mapping: null argument");
+  if (!c->has_ccmap) return fail(PIO_ERR_NOT_READY, "pio_clipcap_mapping: ClipCap mapper (clip_project.model.0 / .2) not loaded");
+  if (!launch_clipcap_mapping) return fail(PIO_ERR_NOT_READY, "pio_clipcap_mapping: built without the kernels");
+  if (N < 1 || N > c->cfg.max_prefixes || N > 128) return fail(PIO_ERR_CAPACITY, "pio_clipcap_mapping: N above min(max_prefixes, 128)");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  const float* x = feats;
+  if (normalize) {           // prefix / prefix.norm(2, -1, keepdim=True) on a copy: the reference does not write through here (:487-488)
+    HIP_OK(hipMemcpyAsync(c->cc_x, feats, (size_t)N * c->cc_C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_OK(launch_l2norm_rows(c->cc_x, N, c->cc_C, s));
+    x = c->cc_x;
+  }
+  HIP_OK(launch_clipcap_mapping(x, N, c->cc_C, c->cc_H, c->cc_Nout, c->cc_w1, c->cc_b1, c->cc_w2, c->cc_b2, c->cc_zeros, c->cc_hid, out, s));
+  return PIO_OK;
+}
+
+int pio_clipcap_prefix_length(pio_handle c) { return (c && c->has_ccmap) ? c->cc_Nout / c->cfg.dec_embd : 0; }
+
+int pio_nucleus_sample(pio_handle c, const float* scores, int32_t N, float temperature, float top_p, const float* uniforms, int32_t stop_id,
+                       int32_t* active, int32_t* tokens, int32_t* kept, pio_stream stream) {
+  if (!c || !scores || !uniforms || !active || !tokens) return fail(PIO_ERR_INVALID_ARG, "pio_nucleus_sample: null argument");
+  if (!launch_nucleus_sample) return fail(PIO_ERR_NOT_READY, "pio_nucleus_sample: built without the kernels");
+  if (N < 1 || c->cfg.dec_vocab < 1) return fail(PIO_ERR_INVALID_ARG, "pio_nucleus_sample: bad shape");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  SampleArgs a;
+  a.scores = scores; a.N = N; a.V = c->cfg.dec_vocab; a.ld = a.V; a.temperature = temperature; a.top_p = top_p; a.uniforms = uniforms;
+  a.u_stride = 1; a.stop_id = stop_id; a.active = active; a.tokens = tokens; a.tok_stride = 1; a.kept = kept;
+  HIP_OK(launch_nucleus_sample(a, (hipStream_t)stream));
+  return PIO_OK;
+}
+
+int pio_lm_sample(pio_handle c, const float* embeds, int32_t N, int32_t P, int32_t steps, float temperature, float top_p, int32_t stop_id,
+                  uint64_t seed, const float* uniforms, int32_t* ids, int32_t* lens, pio_stream stream) {
+  if (!c || !embeds || !ids || !lens) return fail(PIO_ERR_INVALID_ARG, "pio_lm_sample: null argument");
+  if (!c->has_dec) return fail(PIO_ERR_NOT_READY, "pio_lm_sample: language model not loaded");
+  if (!launch_lm_sample || !launch_philox_uniforms) return fail(PIO_ERR_NOT_READY, "pio_lm_sample: built without the kernels");
+  const int cap = c->cfg.max_prefixes < 128 ? c->cfg.max_prefixes : 128;
+  if (N < 1 || P < 1 || steps < 1) return fail(PIO_ERR_INVALID_ARG, "pio_lm_sample: N, P and steps must be positive");
+  if (N > cap) return fail(PIO_ERR_CAPACITY, "pio_lm_sample: N above min(max_prefixes, 128)");
+  if (P + steps - 1 > c->cfg.max_steps) return fail(PIO_ERR_CAPACITY, "pio_lm_sample: prompt + generated positions above max_steps");
+  if (c->cfg.dec_embd != 768 || stop_id < 0 || stop_id >= c->cfg.dec_vocab)
+    return fail(PIO_ERR_INVALID_ARG, "pio_lm_sample: 768-wide language model and a stop id inside the vocabulary required");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = prompted_workspaces(c, c->batched_prefill))) return rc;
+  if (!c->smp_u) {
+    if ((rc = c->dmalloc(&c->smp_u, (size_t)cap * c->cfg.max_steps))) return rc;
+    if ((rc = c->dmalloc(&c->smp_i, (size_t)cap * 2))) return rc;
+  }
+  const size_t E = c->cfg.dec_embd;
+  DecoderArgs a = lm_args(c, N);
+  a.steps = steps; a.pos_base = P - 1;
+  if (c->batched_prefill) { a.pre_x = c->pre_x; a.pre_qkv = c->pre_qkv; a.pre_att = c->pre_att; a.pre_hid = c->pre_hid; a.pre_rows = pio_context::kPrefillRows; }
+  // a captured graph reads the handle's buffers only: the prompt and the uniforms are brought in, the results copied out
+  HIP_OK(hipMemcpyAsync(c->prompt_buf, embeds, (size_t)N * P * E * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (uniforms) HIP_OK(hipMemcpyAsync(c->smp_u, uniforms, (size_t)N * steps * sizeof(float), hipMemcpyDeviceToDevice, s));
+  else HIP_OK(launch_philox_uniforms(seed, N, steps, c->smp_u, s));
+  HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
+  int32_t *active = c->smp_i, *lens_buf = c->smp_i + cap;
+  int32_t tbits, pbits;                                     // temperature, top_p and stop_id are kernel arguments of the graph: part of its key
+  memcpy(&tbits, &temperature, 4); memcpy(&pbits, &top_p, 4);
+  auto launch = [&](hipStream_t cs) { return launch_lm_sample(a, c->prompt_buf, P, temperature, top_p, stop_id, c->smp_u, active, c->bs_f, lens_buf, cs); };
+  if (c->use_graph) {
+    // PKey::ragged = 64 + stop_id (apart from the prompted decodes' 0 / 1 and the beam search's 17 .. 40); eos0 / eos1 carry the bits of
+    // temperature and top_p
+    if ((rc = launch_prompted_graph(c, pio_context::PKey{N, P, steps, 64 + stop_id, tbits, pbits}, launch, s))) return rc;
+  } else {
+    HIP_OK(launch(s));
+  }
+  HIP_OK(hipMemcpyAsync(ids, c->ids_buf, (size_t)N * steps * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemcpyAsync(lens, lens_buf, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  return PIO_OK;
+}
+
 int pio_profile_enable(pio_handle c, int32_t on) {
   if (!c) return fail(PIO_ERR_INVALID_ARG, "null handle");
   HIP_OK(hipSetDevice(c->cfg.device));
@@ -1948,6 +2075,25 @@ int pio_host_interpolate_pos_embed(const float* pos, int32_t grid, int32_t dim, 
 int pio_host_interpolate_pos_embed_plain(const float* pos, int32_t grid, int32_t dim, int32_t n, double offset, float* out) {
   if (!pos || !out || grid < 1 || dim < 1 || n < 1) return fail(PIO_ERR_INVALID_ARG, "pio_host_interpolate_pos_embed_plain: bad argument");
   interpolate_pos_embed_plain(pos, grid, dim, n, offset, out);
+  return PIO_OK;
+}
+
+int pio_host_philox4x32(const uint32_t* ctr, uint32_t key_lo, uint32_t key_hi, uint32_t* out) {
+  if (!ctr || !out) return fail(PIO_ERR_INVALID_ARG, "pio_host_philox4x32: bad argument");
+  philox4x32_10(ctr, key_lo, key_hi, out);
+  return PIO_OK;
+}
+
+int pio_host_philox_uniform(uint64_t seed, uint32_t row, uint32_t step, float* u) {
+  if (!u) return fail(PIO_ERR_INVALID_ARG, "pio_host_philox_uniform: bad argument");
+  *u = philox_uniform(seed, row, step);
+  return PIO_OK;
+}
+
+int pio_host_philox_uniforms(uint64_t seed, uint32_t row0, int32_t N, int32_t steps, float* out) {
+  if (!out || N < 1 || steps < 1) return fail(PIO_ERR_INVALID_ARG, "pio_host_philox_uniforms: bad argument");
+  for (int32_t n = 0; n < N; ++n)
+    for (int32_t k = 0; k < steps; ++k) out[(size_t)n * steps + k] = philox_uniform(seed, row0 + (uint32_t)n, (uint32_t)k);
   return PIO_OK;
 }
 

@@ -146,6 +146,28 @@ struct DeviceOnce {
   }
 };
 
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), plain C++ for host and device alike: the
+// sampler's uniforms (sample.hip) and the host copy the tests compare them with (test_hooks.cpp) are this one function.
+// ctr = the 128-bit counter, key = the 64-bit key (low word first); out = the four output words.
+__host__ __device__ inline void philox4x32_10(const uint32_t ctr[4], uint32_t key_lo, uint32_t key_hi, uint32_t out[4]) {
+  uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key_lo, k1 = key_hi;
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// The sampler's uniform of (row, step) under `seed`: key = seed, counter = (row, step, 0, 0), the first output word's top 24 bits
+// times 2^-24 -- every value is k / 2^24 with k < 2^24, exact in fp32 and inside [0, 1).
+__host__ __device__ inline float philox_uniform(uint64_t seed, uint32_t row, uint32_t step) {
+  const uint32_t ctr[4] = {row, step, 0u, 0u};
+  uint32_t out[4];
+  philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32), out);
+  return (float)(out[0] >> 8) * 5.9604644775390625e-8f;
+}
+
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 

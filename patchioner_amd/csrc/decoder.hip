@@ -86,7 +86,7 @@ static constexpr int DEC_MAX_COLGROUPS = 128;  // split-K counters / slabs: Nout
 static constexpr size_t DEC_SPLITK_WS_FLOATS = (size_t)DEC_SPLITK_COUNTERS * 4 * 8 * 256;   // api.cpp: splitk_ws
 static_assert(DEC_MAX_COLGROUPS == DEC_SPLITK_COUNTERS, "kernels.h");
 
-enum DecEpi { DE_STORE = 0, DE_RESID = 1, DE_GELU = 2, DE_EMBED = 3, DE_ARGMAX = 4 };
+enum DecEpi { DE_STORE = 0, DE_RESID = 1, DE_GELU = 2, DE_EMBED = 3, DE_ARGMAX = 4, DE_TANH = 5 };   // DE_TANH: ClipCap's MLP mapper (k_dec_gemm only)
 
 // diagnostic build only (tools/microbench/dec_bench.hip stamps): shader-clock stamps of wave 0 of every k_dec_gemm workgroup
 #ifdef PIO_DEC_STAMPS
@@ -398,6 +398,7 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? PIO_DEC_GEMM_WAVES : 1) void k
         else if constexpr (EPI == DE_RESID) *o += v;    // each element has exactly one owner: in place is safe
         else if constexpr (EPI == DE_GELU) *o = gelu_new(v);
         else if constexpr (EPI == DE_EMBED) *o = v + ej;
+        else if constexpr (EPI == DE_TANH) *o = tanhf(v);
       }
     }
   }
@@ -2798,6 +2799,77 @@ hipError_t launch_lm_beam_search(const DecoderArgs& a, const BeamArgs& b, hipStr
   }
   hipLaunchKernelGGL(k_beam_finish, dim3(R), dim3(64), 0, s, b.hist, b.scores, b.lens, b.steps, b.ids, b.out_lens, b.out_scores);
   return hipGetLastError();
+}
+
+// ---- ClipCap head (P/src/clipcap/entrypoint.py): the MLP prefix mapper and the sampling decode loop ------------------------------
+// MLP((C, H, Nout)) = Linear, Tanh, Linear (:20-31) on k_dec_gemm, two weight-streaming GEMMs of <= 128 rows.  Layer 1: K = C in one
+// pass with the tanh epilogue.  Layer 2: K = H in 768-wide slices, one launch each -- slice 0 stores (+ bias), the others accumulate in
+// place (DE_RESID with a zero bias), so an element's sum is slice 0 + slice 1 + ... in that order whatever N.  (K is the kernels' row
+// stride; the extent a launch covers is 4 waves x 12 chunks x 16 = 768.)
+hipError_t launch_clipcap_mapping(const float* x, int N, int C, int H, int Nout, const float* w1, const float* b1, const float* w2,
+                                  const float* b2, const float* zeros, float* hid, float* out, hipStream_t s) {
+  if (N < 1 || N > 128 || H < 768 || H % 768 != 0 || Nout < 16 || Nout % 16 != 0) return hipErrorInvalidValue;
+  switch (C) {
+    case 384: PIO_TRY((dec_gemm_rg<6, 1, DE_TANH, 0>(w1, x, N, H, C, b1, hid, nullptr, nullptr, 0.f, nullptr, nullptr, s))); break;
+    case 512: PIO_TRY((dec_gemm_rg<8, 1, DE_TANH, 0>(w1, x, N, H, C, b1, hid, nullptr, nullptr, 0.f, nullptr, nullptr, s))); break;
+    case 640: PIO_TRY((dec_gemm_rg<10, 1, DE_TANH, 0>(w1, x, N, H, C, b1, hid, nullptr, nullptr, 0.f, nullptr, nullptr, s))); break;
+    case 768: PIO_TRY((dec_gemm_rg<12, 1, DE_TANH, 0>(w1, x, N, H, C, b1, hid, nullptr, nullptr, 0.f, nullptr, nullptr, s))); break;
+    case 1024: PIO_TRY((dec_gemm_rg<16, 1, DE_TANH, 0>(w1, x, N, H, C, b1, hid, nullptr, nullptr, 0.f, nullptr, nullptr, s))); break;
+    default: return hipErrorInvalidValue;
+  }
+  PIO_TRY((dec_gemm_rg<12, 1, DE_STORE, 0>(w2, hid, N, Nout, H, b2, out, nullptr, nullptr, 0.f, nullptr, nullptr, s)));
+  for (int k0 = 768; k0 < H; k0 += 768)
+    PIO_TRY((dec_gemm_rg<12, 1, DE_RESID, 0>(w2 + k0, hid + k0, N, Nout, H, zeros, out, nullptr, nullptr, 0.f, nullptr, nullptr, s)));
+  return hipGetLastError();
+}
+
+// x[n][:] = wte[ids[n][step]][:] + wpe[pos][:]
+__global__ __launch_bounds__(256) void k_sample_next_x(const int32_t* __restrict__ ids, int steps, int step, int pos, const float* __restrict__ wte,
+                                                       const float* __restrict__ wpe, int E, int V, float* x) {
+  const int n = blockIdx.x;
+  int t = ids[(size_t)n * steps + step];
+  t = t < 0 ? 0 : (t >= V ? V - 1 : t);
+  for (int d = threadIdx.x; d < E; d += 256) x[(size_t)n * E + d] = wte[(size_t)t * E + d] + wpe[(size_t)pos * E + d];
+}
+
+// generate_batched (:198-311) with a KV cache: the prompt once (launch_decode_prompted's prefill), then per step the exact fp32 LM head on
+// every row (k_row_stats + k_lm_logits_rows: raw logits, the sampler needs no normalisation), k_nucleus_sample, and the drawn token's
+// embedding through the layers.  All a.steps steps run (no early exit: see DESIGN.md); rows that have stopped emit stop_id.
+hipError_t launch_lm_sample(const DecoderArgs& a, const float* prompt, int P, float temperature, float top_p, int stop_id,
+                            const float* uniforms, int32_t* active, float* stats, int32_t* lens, hipStream_t s) {
+  const int N = a.N, E = a.E, V = a.vocab;
+  if (P < 1 || a.steps < 1 || N < 1 || N > 128 || a.pos_base != P - 1 || P + a.steps - 1 > a.max_steps || a.max_steps > 256 || E != 768 ||
+      (E / a.heads) % 32 != 0 || !uniforms || !active || !stats || !lens)
+    return hipErrorInvalidValue;
+  if (a.pre_x != nullptr && P > 1 && P <= a.pre_rows) {
+    const int gmax = a.pre_rows / P;
+    for (int n0 = 0; n0 < N; n0 += gmax) {
+      const int gN = N - n0 < gmax ? N - n0 : gmax;
+      hipLaunchKernelGGL(k_dec_prompt_x_all, dim3(gN, P), dim3(256), 0, s, prompt + (size_t)n0 * P * E, a.wpe, P, E, a.pre_x);
+      PIO_TRY(dec_prefill_layers(a, n0, gN, P, s));
+      hipLaunchKernelGGL(k_dec_last_rows, dim3(gN), dim3(256), 0, s, a.pre_x, P, E, a.x + (size_t)n0 * E);
+    }
+  } else {
+    for (int pos = 0; pos < P; ++pos) {
+      hipLaunchKernelGGL(k_dec_prompt_x, dim3(N), dim3(256), 0, s, prompt, a.wpe, P, pos, E, a.x);
+      PIO_TRY(dec_layers_step(a, pos, s));
+    }
+  }
+  PIO_TRY(launch_sample_init(N, active, s));
+  SampleArgs sa;
+  sa.scores = a.logits; sa.N = N; sa.V = V; sa.ld = V; sa.temperature = temperature; sa.top_p = top_p; sa.u_stride = a.steps;
+  sa.stop_id = stop_id; sa.active = active; sa.tok_stride = a.steps; sa.kept = nullptr;
+  for (int step = 0; step < a.steps; ++step) {
+    hipLaunchKernelGGL(k_row_stats, dim3(N), dim3(256), 0, s, a.x, E, a.eps, stats);
+    hipLaunchKernelGGL(k_lm_logits_rows, dim3(ceil_div(V, 4 * BL_C)), dim3(256), 0, s, a.head_w, a.x, N, V, a.head_d, a.head_c, stats, a.logits);
+    sa.uniforms = uniforms + step; sa.tokens = a.ids + step;
+    PIO_TRY(launch_nucleus_sample(sa, s));
+    if (step + 1 < a.steps) {
+      hipLaunchKernelGGL(k_sample_next_x, dim3(N), dim3(256), 0, s, a.ids, a.steps, step, P + step, a.wte, a.wpe, E, V, a.x);
+      PIO_TRY(dec_layers_step(a, P + step, s));
+    }
+  }
+  return launch_sample_lens(a.ids, N, a.steps, stop_id, lens, s);
 }
 
 }  // namespace pio

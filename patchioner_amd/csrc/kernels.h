@@ -300,6 +300,33 @@ struct BeamArgs {
 hipError_t launch_lm_beam_search(const DecoderArgs& a, const BeamArgs& b, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// ClipCap head: nucleus sampling (sample.hip), the sampling decode loop and the MLP prefix mapper (decoder.hip)
+// ---------------------------------------------------------------------------------------------
+// One token per row of scores [N][ld] (V <= ld valid columns; raw logits or log-probabilities: a per-row constant is immaterial).
+// Row n: inactive -> stop_id; NaN / inf anywhere -> stop_id; otherwise the top-p draw with uniform uniforms[n * u_stride] (sample.hip).
+struct SampleArgs {
+  const float* scores; int N, V, ld;
+  float temperature, top_p;
+  const float* uniforms; int u_stride;
+  int stop_id;
+  int32_t* active;            // [N] in / out
+  int32_t* tokens; int tok_stride;
+  int32_t* kept;              // [N] kept-set sizes, or null
+};
+hipError_t launch_nucleus_sample(const SampleArgs& a, hipStream_t s);
+hipError_t launch_philox_uniforms(uint64_t seed, int N, int steps, float* u, hipStream_t s);     // u[n][k] = philox_uniform(seed, n, k)
+hipError_t launch_sample_init(int N, int32_t* active, hipStream_t s);
+hipError_t launch_sample_lens(const int32_t* ids, int N, int steps, int stop_id, int32_t* lens, hipStream_t s);
+// prompt embeds [N][P][E] -> a.steps sampled tokens per row into a.ids [N][steps] (a.pos_base = P - 1; a.logits: [N][V] raw logits
+// scratch; stats [N][2]); uniforms [N][steps] and active [N] on the device.  Every step runs; stopped rows emit stop_id.
+hipError_t launch_lm_sample(const DecoderArgs& a, const float* prompt, int P, float temperature, float top_p, int stop_id,
+                            const float* uniforms, int32_t* active, float* stats, int32_t* lens, hipStream_t s);
+// ClipCap's MLP mapper: out [N][Nout] = tanh(x W1^T + b1) W2^T + b2 on the decode GEMM family; W1 [H][C], W2 [Nout][H] (nn.Linear
+// layouts), H and Nout multiples of 768 / 16, C in {384, 512, 640, 768, 1024}; hid: [N][H] scratch, zeros: [Nout] zeros; N <= 128
+hipError_t launch_clipcap_mapping(const float* x, int N, int C, int H, int Nout, const float* w1, const float* b1, const float* w2,
+                                  const float* b2, const float* zeros, float* hid, float* out, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // ViECap head (viecap.hip): mapping network, entity logits, prompt assembly -- all fp32
 // ---------------------------------------------------------------------------------------------
 struct ViecapMapLayerW {

@@ -202,4 +202,16 @@ int pio_test_attnpool_in(int32_t operand, const void* x, const float* pos, int32
   return PIO_OK;
 }
 
+int pio_test_nucleus_sample(const float* scores, int32_t N, int32_t V, float temperature, float top_p, const float* uniforms, int32_t stop_id,
+                            int32_t* active, int32_t* tokens, int32_t* kept, pio_stream stream) {
+  if (!scores || !uniforms || !active || !tokens || N < 1 || V < 1)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_nucleus_sample: scores, uniforms, active, tokens, N >= 1, V >= 1");
+  SampleArgs a;
+  a.scores = scores; a.N = N; a.V = V; a.ld = V; a.temperature = temperature; a.top_p = top_p; a.uniforms = uniforms; a.u_stride = 1;
+  a.stop_id = stop_id; a.active = active; a.tokens = tokens; a.tok_stride = 1; a.kept = kept;
+  const hipError_t e = launch_nucleus_sample(a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_nucleus_sample: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
 }  // extern "C"

@@ -95,6 +95,8 @@ def _id_columns(model) -> int:
     steps for the DeCap / CapDec decoder (decap.py:116), 64 for the ViECap greedy search (search.py:108-191)."""
     if getattr(model, "calculate_argmax_text", False):
         raise ValueError("sharded captioning gathers token ids; a calculate_argmax_text model returns bank texts and has none")
+    if getattr(model, "clipcap", None) is not None:
+        raise NotImplementedError("sharded captioning of a ClipCap head (sampled ids, entry_length columns) is not built")
     head = getattr(model, "viecap", None)
     if head is not None and not getattr(getattr(head, "args", None), "using_greedy_search", True):
         raise ValueError("sharded captioning gathers the greedy search's token ids; a beam-search ViECap head returns sentences only")

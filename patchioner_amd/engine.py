@@ -594,6 +594,56 @@ class Engine:
         prompt, plen = self.viecap_build_prompt_ragged(cont, tokens, lens, soft_first=soft_first)
         return self.lm_beam_search(prompt, plen, beam_width, eos, steps=steps)
 
+    # ------------------------------------------------------------------ ClipCap head: MLP mapper, nucleus sampling, sampling loop
+    def clipcap_mapping(self, feats: torch.Tensor, normalize: bool = False) -> torch.Tensor:
+        """feats [N, C] -> prefix [N, Lp, E] (pio_clipcap_mapping); ``normalize``: rows L2-normalised first, on a copy."""
+        feats = self._dev(feats).contiguous()
+        N = int(feats.shape[0])
+        Lp = int(self.lib.pio_clipcap_prefix_length(self.h))
+        out = torch.empty(N, Lp, self.cfg.dec_embd, device=self.device, dtype=torch.float32)
+        cap = min(self.max_prefixes, 128)
+        for s in range(0, N, cap):
+            e = min(N, s + cap)
+            check(self.lib.pio_clipcap_mapping(self.h, ptr(feats[s:e]), e - s, 1 if normalize else 0, ptr(out[s:e]), _stream()))
+        return out
+
+    def nucleus_sample(self, scores: torch.Tensor, uniforms: torch.Tensor, temperature: float, top_p: float, stop_id: int,
+                       active: Optional[torch.Tensor] = None):
+        """One top-p draw per row of scores [N, vocab] (pio_nucleus_sample) -> (tokens [N], active [N], kept-set sizes [N]), int32, device."""
+        scores, uniforms = self._dev(scores).contiguous(), self._dev(uniforms).contiguous()
+        N = int(scores.shape[0])
+        act = torch.ones(N, device=self.device, dtype=torch.int32) if active is None else self._dev(active, torch.int32).clone()
+        tok = torch.empty(N, device=self.device, dtype=torch.int32)
+        kept = torch.empty(N, device=self.device, dtype=torch.int32)
+        check(self.lib.pio_nucleus_sample(self.h, ptr(scores), N, float(temperature), float(top_p), ptr(uniforms), int(stop_id), ptr(act),
+                                          ptr(tok), ptr(kept), _stream()))
+        return tok, act, kept
+
+    def lm_sample(self, embeds: torch.Tensor, steps: int, temperature: float, top_p: float, stop_id: int, seed: int = 0,
+                  uniforms: Optional[torch.Tensor] = None, rows_per_call: Optional[int] = None):
+        """embeds [N, P, E] -> (ids [N, steps] int32, lens [N] int32) on the device (pio_lm_sample): enqueue-only.  ``uniforms`` [N, steps]
+        or None: Philox under ``seed`` with counter (row, step, 0, 0), row counted over the WHOLE batch.  Calls of min(max_prefixes, 128)
+        rows, or ``rows_per_call``; a batch that needs more than one call gets its uniforms from the host copy of the generator
+        (pio_host_philox_uniforms), since a call counts its rows from 0 -- the ids do not depend on how the batch is split."""
+        embeds = self._dev(embeds).contiguous()
+        N, P = int(embeds.shape[0]), int(embeds.shape[1])
+        ids = torch.empty(N, steps, device=self.device, dtype=torch.int32)
+        lens = torch.empty(N, device=self.device, dtype=torch.int32)
+        cap = min(self.max_prefixes, 128)
+        if rows_per_call is not None:
+            cap = max(1, min(cap, int(rows_per_call)))
+        if uniforms is None and N > cap:
+            uniforms = torch.empty(N, steps, dtype=torch.float32)
+            check(self.lib.pio_host_philox_uniforms(int(seed) & 0xFFFFFFFFFFFFFFFF, 0, N, int(steps), ptr(uniforms)))
+        if uniforms is not None:
+            uniforms = self._dev(uniforms).contiguous()
+        for s in range(0, N, cap):
+            e = min(N, s + cap)
+            check(self.lib.pio_lm_sample(self.h, ptr(embeds[s:e]), e - s, P, int(steps), float(temperature), float(top_p), int(stop_id),
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(uniforms[s:e]) if uniforms is not None else None, ptr(ids[s:e]),
+                                         ptr(lens[s:e]), _stream()))
+        return ids, lens
+
     # ------------------------------------------------------------------ a11/a12 decoder
     def decode_greedy(self, prefix: torch.Tensor, steps: int = 30, want_logprob: bool = False):
         prefix = self._dev(prefix)
@@ -638,3 +688,4 @@ class DecoderClone:
     lm_beam_search = Engine.lm_beam_search
     viecap_build_prompt_ragged = Engine.viecap_build_prompt_ragged
     viecap_beam_ragged = Engine.viecap_beam_ragged
+    lm_sample = Engine.lm_sample

@@ -39,7 +39,7 @@ from .engine import Engine
 from .preprocess import make_transforms
 from .tokenizer import ClipDetokenizer
 
-_OUT_OF_SCOPE = ("proxyclip_clipmodel", "denseclip_config", "clipcap_config")
+_OUT_OF_SCOPE = ("proxyclip_clipmodel", "denseclip_config")
 
 
 def _load_state_dict(spec):
@@ -197,10 +197,15 @@ class Patchioner(nn.Module):
                  vit_dtype="fp16", memory_bank_texts=None, clip_text_weights=None, clip_text_dtype="fp16",
                  talk2dino_projection_weights=None, **kwargs):
         super().__init__(**kwargs)
-        given = dict(proxyclip_clipmodel=proxyclip_clipmodel, denseclip_config=denseclip_config, clipcap_config=clipcap_config)
+        given = dict(proxyclip_clipmodel=proxyclip_clipmodel, denseclip_config=denseclip_config)
         for k in _OUT_OF_SCOPE:
             if given[k] is not None:
                 raise NotImplementedError("%s: backbone/head outside the MI355X hot-path scope (DINOv2 + DeCap/CapDec)" % k)
+        if clipcap_config is not None:
+            # the ClipCap head's config is checked strictly, before anything touches the device, the weights or the tokenizer: a key
+            # the head does not implement raises NotImplementedError naming it (the reference ignores unknown keys)
+            from .clipcap import validate_config as _validate_clipcap
+            clipcap_config = _validate_clipcap(clipcap_config)
         if use_open_clip:
             raise NotImplementedError("use_open_clip: OpenCLIP text-tower weights are not supported (the OpenAI CLIP text tower "
                                       "is: online_texts, bank.build_memory_bank)")
@@ -250,7 +255,7 @@ class Patchioner(nn.Module):
             raise AssertionError("Input height (%d) doesn't match model (%d)." % (crop_dim, resize_dim))
         if viecap_config is not None and viecap_config.get('meacap', False):
             raise NotImplementedError("MeaCap head (retrieved-caption scene graphs, flan-T5): outside the hot-path scope")
-        if decoder_weights is None and synthetic_seed is None and not calculate_argmax_text and viecap_config is None:
+        if decoder_weights is None and synthetic_seed is None and not calculate_argmax_text and viecap_config is None and clipcap_config is None:
             raise ValueError("decap_weights is required (or synthetic_seed for seeded synthetic weights)")
         self.decoding_method = None
         self.viecap = None
@@ -350,6 +355,23 @@ class Patchioner(nn.Module):
             from .viecap import load_viecap_weights
             viecap_sd = load_viecap_weights(viecap_config)
             dec_sd = None
+        clipcap_tok = None
+        # with a ViECap block as well, the reference's caption_tokens tests viecap first (P/src/model.py:1394-1404): its ClipCap head is
+        # built and never reached.  Here it is validated (above) and not built.
+        if clipcap_config is not None and viecap_config is None:
+            # P/src/model.py:115-121, 1399-1404: the ClipCap head replaces the DeCap decode; as for ViECap the engine holds ONE language
+            # model, the checkpoint's GPT-2 (`gpt.*`), next to its MLP mapper (`clip_project.model.0 / .2`)
+            from .clipcap import load_clipcap_weights, resolve_tokenizer
+            clipcap_tok = resolve_tokenizer(clipcap_config)
+            from .clipcap import DEFAULTS as _CLIPCAP_DEFAULTS
+            if clipcap_config.get("weights") is None and synthetic_seed is not None and clipcap_config["weight_path"] == _CLIPCAP_DEFAULTS["weight_path"]:
+                # the vocabulary is the tokenizer's: a sampled id (unlike a random-weight arg-max) would leave a smaller one
+                nv = len(clipcap_tok) if hasattr(clipcap_tok, "__len__") else 50257
+                viecap_sd = W.synth_clipcap(synthetic_seed + 2, C=self.token_dim, prefix_length=int(clipcap_config["prefix_length"]),
+                                            vocab=nv, tok_vocab=nv)
+            else:
+                viecap_sd = load_clipcap_weights(clipcap_config)
+            dec_sd = None
 
         self.embed_inversion = talk2dino_weights is not None
         inv_sd = {}
@@ -390,13 +412,16 @@ class Patchioner(nn.Module):
         if dec_sd is not None:                         # calculate_argmax_text without decoder weights: no decoder (model.py:165)
             self.engine.load_state_dict(dec_sd)        # strict=False like the reference (decap.py:214)
         if viecap_sd is not None:
-            self.engine.load_state_dict({k: v for k, v in viecap_sd.items() if k.startswith(("mapping_network.", "gpt."))})
+            self.engine.load_state_dict({k: v for k, v in viecap_sd.items() if k.startswith(("mapping_network.", "gpt.", "clip_project.model."))})
         if inv_sd:
             self.engine.load_state_dict(inv_sd)
         self.engine.finalize()
         if viecap_config is not None:
             from .viecap import VieCapHead
             self.viecap = VieCapHead(viecap_config, self.engine, clip_model_name)
+        elif clipcap_config is not None:
+            from .clipcap import ClipCapHead
+            self.clipcap = ClipCapHead(clipcap_config, self.engine, tokenizer=clipcap_tok)
 
         if support_memory_size > 0:
             if online_texts is not None:
@@ -957,6 +982,21 @@ class Patchioner(nn.Module):
             out = self.viecap.forward(dino_tokens, compute_scores=compute_scores)
             self.last_ids = self.viecap.last_ids      # [N, 64] ids of the greedy search: what dist.sharded_* gathers
             return out
+        if self.clipcap is not None:
+            if return_n_best_sims:
+                raise Exception("return_n_best_sims is not supported with clipcap")
+            if self._defer:
+                # forward_async: the mapper and pio_lm_sample are enqueue-only; ids -> text in result()
+                if compute_scores:
+                    raise NotImplementedError("forward_async does not defer score lists; call forward() for compute_scores")
+                ids = self.clipcap.enqueue(dino_tokens)
+                self.last_ids = ids
+                if ids is None:                        # entry_length 0: nothing to wait for
+                    return [""] * int(dino_tokens.shape[0])
+                return _PendingClipCapCaptions(ids, self.clipcap)
+            out = self.clipcap.forward(dino_tokens, compute_scores=compute_scores)
+            self.last_ids = self.clipcap.last_ids
+            return out
         if self.im_proj is None:
             project = False
         x = dino_tokens
@@ -1044,6 +1084,17 @@ class _PendingCaptions:
 
 class _PendingVieCapCaptions(_PendingCaptions):
     """Greedy ids of the ViECap head still on the device; resolved as VieCapHead.forward would return them (a single row: a str)."""
+
+    def __init__(self, ids_dev, head):
+        super().__init__(ids_dev, None, None)
+        self.head = head
+
+    def resolve(self):
+        return self.head.captions(self.ids_host.tolist())
+
+
+class _PendingClipCapCaptions(_PendingCaptions):
+    """Sampled ids of the ClipCap head still on the device; resolved as ClipCapHead.forward returns them (always a list)."""
 
     def __init__(self, ids_dev, head):
         super().__init__(ids_dev, None, None)

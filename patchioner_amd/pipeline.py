@@ -108,6 +108,8 @@ class TraceCaptionPipeline:
         so that one batch's GEMM tails, epilogues and launch gaps are filled by the other's kernels."""
         if getattr(model, "backbone_type", None) == 'AlphaClip':
             raise NotImplementedError("AlphaCLIP region captions (a tower pass per region) are not pipelined; call forward(traces=...)")
+        if getattr(model, "clipcap", None) is not None:
+            raise NotImplementedError("the ClipCap head (sampling decode) is not pipelined; call forward() or forward_async()")
         self.m, self.eng = model, model.engine
         self.stage_models = [model] + list(stage_replicas)
         self.viecap = getattr(model, "viecap", None)

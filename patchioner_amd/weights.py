@@ -530,6 +530,22 @@ def synth_viecap(seed: int, clip_hidden_size: int = 768, n_layer: int = 12, n_em
     return w
 
 
+def synth_clipcap(seed: int, C: int = 768, prefix_length: int = 10, n_layer: int = 12, n_embd: int = 768, vocab: int = 50257,
+                  n_positions: int = 1024, tok_vocab: int = 50257, std: float = 0.02) -> Dict[str, torch.Tensor]:
+    """State dict shaped like the reference's ClipCap checkpoint with the MLP mapper (P/src/clipcap/entrypoint.py:20-31, 140-181):
+    ``clip_project.model.0.*`` (Linear C -> prefix_length x n_embd / 2), ``clip_project.model.2.*`` (Linear -> prefix_length x n_embd)
+    and ``gpt.*``, generated as for ViECap (synth_viecap)."""
+    w = {k: v for k, v in synth_viecap(seed, n_layer=n_layer, n_embd=n_embd, vocab=vocab, n_positions=n_positions, tok_vocab=tok_vocab,
+                                       map_layers=0, std=std).items() if k.startswith("gpt.")}
+    g = torch.Generator().manual_seed(seed + 7919)
+    H, O = prefix_length * n_embd // 2, prefix_length * n_embd
+    w["clip_project.model.0.weight"] = torch.randn(H, C, generator=g) * (1.0 / C ** 0.5)
+    w["clip_project.model.0.bias"] = torch.randn(H, generator=g) * 0.1
+    w["clip_project.model.2.weight"] = torch.randn(O, H, generator=g) * (0.5 / H ** 0.5)
+    w["clip_project.model.2.bias"] = torch.randn(O, generator=g) * 0.1
+    return w
+
+
 SYNTH_ENTITIES = ["person", "bicycle", "car", "motorcycle", "airplane", "bus", "train", "truck", "boat", "traffic light",
                   "fire hydrant", "stop sign", "bench", "bird", "cat", "dog", "horse", "sheep", "cow", "elephant", "bear", "zebra",
                   "giraffe", "backpack", "umbrella", "handbag", "tie", "suitcase", "frisbee", "skis", "kite", "baseball bat"]
