@@ -10,6 +10,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -182,14 +183,17 @@ struct pio_context {
   static constexpr int kPrefillRows = 2048;
   int32_t* tok_buf = nullptr;                     // [max_prefixes][max_steps]
   int32_t* plen_buf = nullptr;                    // [max_prefixes] prompt length per row of a ragged decode (pio_viecap_decode_ragged)
-  // ragged: a pio_viecap_decode_ragged graph (P = the upper bound Pmax; the lengths are read from plen_buf)
+  // Which decode a cached graph holds, and every launch parameter that is baked into its kernel arguments: the shape (N, P, steps) and the
+  // parameters of its kind.  P of a RAGGED / BEAM graph is the upper bound Pmax; the lengths themselves are read from the device.
+  enum PKind { PROMPTED, RAGGED, BEAM, SAMPLE };
   struct PKey {
-    int N, P, steps, ragged;
-    int eos0 = 0, eos1 = 0;        // batched beam search: its end-of-sentence ids are kernel arguments of the graph
+    PKind kind;
+    int N, P, steps;
+    int W = 0, has_plen = 0, eos0 = 0, eos1 = 0;                 // BEAM: beam width, whether prompt lengths were given, end-of-sentence ids
+    int stop_id = 0; uint32_t temp_bits = 0, top_p_bits = 0;     // SAMPLE: stop token, the bits of temperature and top_p
     bool operator<(const PKey& o) const {
-      if (N != o.N || P != o.P || steps != o.steps || ragged != o.ragged)
-        return N != o.N ? N < o.N : (P != o.P ? P < o.P : (steps != o.steps ? steps < o.steps : ragged < o.ragged));
-      return eos0 != o.eos0 ? eos0 < o.eos0 : eos1 < o.eos1;
+      return std::tie(kind, N, P, steps, W, has_plen, eos0, eos1, stop_id, temp_bits, top_p_bits) <
+             std::tie(o.kind, o.N, o.P, o.steps, o.W, o.has_plen, o.eos0, o.eos1, o.stop_id, o.temp_bits, o.top_p_bits);
     }
   };
   // prompted-decode graphs, keyed by (rows, prompt positions, steps).  The prompt length follows the hard prompt of every batch,
@@ -578,7 +582,6 @@ int finalize_decoder(pio_context* c) {
       }
     }
   }
-  HIP_OK(decoder_init());
   if ((rc = alloc_decoder_workspaces(c))) return rc;
   c->has_dec = true;
   return PIO_OK;
@@ -1404,6 +1407,46 @@ int pio_revert_transformation(pio_handle c, const float* x, int32_t N, float* ou
   return PIO_OK;
 }
 
+// DecoderArgs of `N` rows over the handle's language model and workspaces: the only place they are filled.  steps / pos_base / logprob as
+// DecoderArgs documents them; the batched-prefill workspace is added by with_prefill.
+static DecoderArgs lm_args(pio_context* c, int N, int steps = 1, int pos_base = 0, bool logprob = false) {
+  DecoderArgs a;
+  a.N = N; a.steps = steps; a.E = c->cfg.dec_embd; a.heads = c->cfg.dec_heads; a.layers = c->cfg.dec_layers; a.vocab = c->cfg.dec_vocab;
+  a.prefix_size = c->cfg.prefix_size; a.eps = c->cfg.dec_ln_eps; a.prefix = c->prefix_buf; a.clip_w = c->clip_w; a.clip_b = c->clip_b;
+  a.wte = c->wte; a.wpe = c->wpe; a.head_w = c->head_w; a.head_c = c->head_c; a.head_d = c->head_d; a.layer = c->dl.data();
+  a.x = c->dx; a.qkv = c->dqkv; a.att = c->datt; a.hid = c->dhid; a.splitk_ws = c->splitk_ws; a.splitk_cnt = c->splitk_cnt; a.lm_tail = c->lm_tail ? 1 : 0;
+  a.kcache = c->kcache; a.vcache = c->vcache; a.max_steps = c->cfg.max_steps; a.logits = c->logits; a.ids = c->ids_buf;
+  a.logprob = logprob ? c->logprob_buf : nullptr;
+  a.head_w16 = c->head_w16; a.head_w16_unscale = c->head_w16_unscale; a.head_bound_coef = c->head_bound_coef;
+  a.xh = c->dec_xh; a.lm_stats = c->lm_stats; a.lm_gmax = c->lm_gmax; a.pos_base = pos_base;
+  return a;
+}
+
+// the batched prompt prefill's workspace (prompted_workspaces(c, true) has allocated it)
+static void with_prefill(DecoderArgs& a, const pio_context* c) {
+  a.pre_x = c->pre_x; a.pre_qkv = c->pre_qkv; a.pre_att = c->pre_att; a.pre_hid = c->pre_hid; a.pre_rows = pio_context::kPrefillRows;
+}
+
+// launch(stream) captured on the handle's capture stream and instantiated -> *exec.  what: the decode's name in the error message.
+extern "C++" {
+template <class F>
+static int capture_exec(pio_context* c, F launch, const char* what, hipGraphExec_t* exec) {
+  hipGraph_t graph = nullptr;
+  HIP_OK(hipStreamBeginCapture(c->capture_stream, hipStreamCaptureModeThreadLocal));
+  hipError_t le = launch(c->capture_stream);
+  hipError_t ce = hipStreamEndCapture(c->capture_stream, &graph);
+  if (le != hipSuccess) {
+    if (graph) (void)hipGraphDestroy(graph);
+    return fail(PIO_ERR_HIP, std::string(what) + " capture: " + hipGetErrorString(le));
+  }
+  HIP_OK(ce);
+  const hipError_t ie = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  HIP_OK(ie);
+  return PIO_OK;
+}
+}  // extern "C++"
+
 int pio_decode_greedy(pio_handle c, const float* prefix, int32_t N, int32_t steps, int32_t* ids, float* logprob,
                       pio_stream stream) {
   if (!c || !prefix || !ids) return fail(PIO_ERR_INVALID_ARG, "pio_decode_greedy: null argument");
@@ -1414,14 +1457,7 @@ int pio_decode_greedy(pio_handle c, const float* prefix, int32_t N, int32_t step
   HIP_OK(hipSetDevice(c->cfg.device));
   hipStream_t s = (hipStream_t)stream;
   const int E = c->cfg.dec_embd, PS = c->cfg.prefix_size;
-  DecoderArgs a;
-  a.N = N; a.steps = steps; a.E = E; a.heads = c->cfg.dec_heads; a.layers = c->cfg.dec_layers; a.vocab = c->cfg.dec_vocab;
-  a.prefix_size = PS; a.eps = c->cfg.dec_ln_eps; a.prefix = c->prefix_buf; a.clip_w = c->clip_w; a.clip_b = c->clip_b;
-  a.wte = c->wte; a.wpe = c->wpe; a.head_w = c->head_w; a.head_c = c->head_c; a.head_d = c->head_d; a.layer = c->dl.data();
-  a.x = c->dx; a.qkv = c->dqkv; a.att = c->datt; a.hid = c->dhid; a.splitk_ws = c->splitk_ws; a.splitk_cnt = c->splitk_cnt; a.lm_tail = c->lm_tail ? 1 : 0; a.kcache = c->kcache; a.vcache = c->vcache;
-  a.max_steps = c->cfg.max_steps; a.logits = c->logits; a.ids = c->ids_buf; a.logprob = logprob ? c->logprob_buf : nullptr;
-  a.head_w16 = c->head_w16; a.head_w16_unscale = c->head_w16_unscale; a.head_bound_coef = c->head_bound_coef;
-  a.xh = c->dec_xh; a.lm_stats = c->lm_stats; a.lm_gmax = c->lm_gmax;
+  const DecoderArgs a = lm_args(c, N, steps, 0, logprob != nullptr);
   HIP_OK(hipMemcpyAsync(c->prefix_buf, prefix, (size_t)N * PS * 4, hipMemcpyDeviceToDevice, s));
   HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));   // tickets start at zero whatever happened before
   // algorithmic work of a KV-cached decode: per token 4 layers x 12 E^2 MACs + the tied LM head;
@@ -1435,19 +1471,9 @@ int pio_decode_greedy(pio_handle c, const float* prefix, int32_t N, int32_t step
     const GraphKey key{N, steps, logprob ? 1 : 0};
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
-      hipGraph_t graph = nullptr;
-      HIP_OK(hipStreamBeginCapture(c->capture_stream, hipStreamCaptureModeThreadLocal));
-      hipError_t le = launch_decode_greedy(a, c->capture_stream);
-      hipError_t ce = hipStreamEndCapture(c->capture_stream, &graph);
-      if (le != hipSuccess) {
-        if (graph) (void)hipGraphDestroy(graph);
-        return fail(PIO_ERR_HIP, std::string("decode capture: ") + hipGetErrorString(le));
-      }
-      HIP_OK(ce);
       hipGraphExec_t exec = nullptr;
-      const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      HIP_OK(ie);
+      int rc = capture_exec(c, [&](hipStream_t cs) { return launch_decode_greedy(a, cs); }, "decode", &exec);
+      if (rc) return rc;
       it = c->graphs.emplace(key, exec).first;
     }
     PROF(c, PIO_PROF_DECODE, dec_flops, dec_bytes, s, hipGraphLaunch(it->second, s));
@@ -1509,30 +1535,10 @@ int pio_lm_score(pio_handle c, const int32_t* tokens, const int32_t* lens, int32
   if (Lmax < 1 || Lmax > c->cfg.max_steps || Lmax > 256) return fail(PIO_ERR_CAPACITY, "pio_lm_score: Lmax above max_steps");
   HIP_OK(hipSetDevice(c->cfg.device));
   hipStream_t s = (hipStream_t)stream;
-  DecoderArgs a;
-  a.N = N; a.steps = 1; a.E = c->cfg.dec_embd; a.heads = c->cfg.dec_heads; a.layers = c->cfg.dec_layers; a.vocab = c->cfg.dec_vocab;
-  a.prefix_size = c->cfg.prefix_size; a.eps = c->cfg.dec_ln_eps; a.prefix = nullptr; a.clip_w = nullptr; a.clip_b = nullptr;
-  a.wte = c->wte; a.wpe = c->wpe; a.head_w = c->head_w; a.head_c = c->head_c; a.head_d = c->head_d; a.layer = c->dl.data();
-  a.x = c->dx; a.qkv = c->dqkv; a.att = c->datt; a.hid = c->dhid; a.splitk_ws = c->splitk_ws; a.splitk_cnt = c->splitk_cnt; a.lm_tail = c->lm_tail ? 1 : 0;
-  a.kcache = c->kcache; a.vcache = c->vcache; a.max_steps = c->cfg.max_steps; a.logits = c->logits; a.ids = c->ids_buf; a.logprob = nullptr;
-  a.head_w16 = c->head_w16; a.head_w16_unscale = c->head_w16_unscale; a.head_bound_coef = c->head_bound_coef;
-  a.xh = c->dec_xh; a.lm_stats = c->lm_stats; a.lm_gmax = c->lm_gmax; a.pos_base = 0;
+  const DecoderArgs a = lm_args(c, N);
   HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
   HIP_OK(launch_lm_score(a, tokens, lens, Lmax, nll, s));
   return PIO_OK;
-}
-
-// DecoderArgs of a single-position / prompt pass over the handle's language model (no greedy loop)
-static DecoderArgs lm_args(pio_context* c, int N) {
-  DecoderArgs a;
-  a.N = N; a.steps = 1; a.E = c->cfg.dec_embd; a.heads = c->cfg.dec_heads; a.layers = c->cfg.dec_layers; a.vocab = c->cfg.dec_vocab;
-  a.prefix_size = c->cfg.prefix_size; a.eps = c->cfg.dec_ln_eps; a.prefix = nullptr; a.clip_w = nullptr; a.clip_b = nullptr;
-  a.wte = c->wte; a.wpe = c->wpe; a.head_w = c->head_w; a.head_c = c->head_c; a.head_d = c->head_d; a.layer = c->dl.data();
-  a.x = c->dx; a.qkv = c->dqkv; a.att = c->datt; a.hid = c->dhid; a.splitk_ws = c->splitk_ws; a.splitk_cnt = c->splitk_cnt; a.lm_tail = c->lm_tail ? 1 : 0;
-  a.kcache = c->kcache; a.vcache = c->vcache; a.max_steps = c->cfg.max_steps; a.logits = c->logits; a.ids = c->ids_buf; a.logprob = nullptr;
-  a.head_w16 = c->head_w16; a.head_w16_unscale = c->head_w16_unscale; a.head_bound_coef = c->head_bound_coef;
-  a.xh = c->dec_xh; a.lm_stats = c->lm_stats; a.lm_gmax = c->lm_gmax; a.pos_base = 0;
-  return a;
 }
 
 static int beam_scratch(pio_context* c) {
@@ -1620,19 +1626,9 @@ template <class F>
 static int launch_prompted_graph(pio_context* c, const pio_context::PKey& key, F launch, hipStream_t s) {
   auto it = c->pgraphs.find(key);
   if (it == c->pgraphs.end()) {
-    hipGraph_t graph = nullptr;
-    HIP_OK(hipStreamBeginCapture(c->capture_stream, hipStreamCaptureModeThreadLocal));
-    hipError_t le = launch(c->capture_stream);
-    hipError_t ce = hipStreamEndCapture(c->capture_stream, &graph);
-    if (le != hipSuccess) {
-      if (graph) (void)hipGraphDestroy(graph);
-      return fail(PIO_ERR_HIP, std::string("prompted decode capture: ") + hipGetErrorString(le));
-    }
-    HIP_OK(ce);
     hipGraphExec_t exec = nullptr;
-    hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    HIP_OK(ie);
+    int rc = capture_exec(c, launch, "prompted decode", &exec);
+    if (rc) return rc;
     if (c->pgraphs.size() >= pio_context::kMaxPGraphs) {       // evict the least recently used graph
       auto old = c->pgraphs.begin();
       for (auto jt = c->pgraphs.begin(); jt != c->pgraphs.end(); ++jt)
@@ -1692,18 +1688,11 @@ int pio_viecap_decode(pio_handle c, const float* cont, const int32_t* tokens, in
   if ((rc = prompted_workspaces(c, batched_prefill))) return rc;
   if (Lt > 0) HIP_OK(hipMemcpyAsync(c->tok_buf, tokens, (size_t)N * Lt * 4, hipMemcpyDeviceToDevice, s));
   HIP_OK(launch_build_prompt(cont, c->tok_buf, c->wte, N, Lc, Lt, E, c->cfg.dec_vocab, soft_first, c->prompt_buf, s));
-  DecoderArgs a;
-  a.N = N; a.steps = steps; a.E = E; a.heads = c->cfg.dec_heads; a.layers = c->cfg.dec_layers; a.vocab = c->cfg.dec_vocab;
-  a.prefix_size = c->cfg.prefix_size; a.eps = c->cfg.dec_ln_eps; a.prefix = nullptr; a.clip_w = nullptr; a.clip_b = nullptr;
-  a.wte = c->wte; a.wpe = c->wpe; a.head_w = c->head_w; a.head_c = c->head_c; a.head_d = c->head_d; a.layer = c->dl.data();
-  a.x = c->dx; a.qkv = c->dqkv; a.att = c->datt; a.hid = c->dhid; a.splitk_ws = c->splitk_ws; a.splitk_cnt = c->splitk_cnt; a.lm_tail = c->lm_tail ? 1 : 0;
-  a.kcache = c->kcache; a.vcache = c->vcache; a.max_steps = c->cfg.max_steps; a.logits = c->logits; a.ids = c->ids_buf; a.logprob = nullptr;
-  a.head_w16 = c->head_w16; a.head_w16_unscale = c->head_w16_unscale; a.head_bound_coef = c->head_bound_coef;
-  a.xh = c->dec_xh; a.lm_stats = c->lm_stats; a.lm_gmax = c->lm_gmax; a.pos_base = P - 1;
-  if (batched_prefill) { a.pre_x = c->pre_x; a.pre_qkv = c->pre_qkv; a.pre_att = c->pre_att; a.pre_hid = c->pre_hid; a.pre_rows = pio_context::kPrefillRows; }
+  DecoderArgs a = lm_args(c, N, steps, P - 1);
+  if (batched_prefill) with_prefill(a, c);
   HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
   if (c->use_graph) {
-    int rc2 = launch_prompted_graph(c, pio_context::PKey{N, P, steps, 0},
+    int rc2 = launch_prompted_graph(c, pio_context::PKey{pio_context::PROMPTED, N, P, steps},
                                     [&](hipStream_t cs) { return launch_decode_prompted(a, c->prompt_buf, P, cs); }, s);
     if (rc2) return rc2;
   } else {
@@ -1755,20 +1744,13 @@ int pio_viecap_decode_ragged(pio_handle c, const float* cont, const int32_t* tok
   if (!c->plen_buf && (rc = c->dmalloc(&c->plen_buf, (size_t)c->cfg.max_prefixes))) return rc;
   HIP_OK(launch_build_prompt_ragged(cont, tokens, Ltmax > 0 ? lens : nullptr, c->wte, N, Lc, Ltmax, E, c->cfg.dec_vocab, soft_first,
                                     c->prompt_buf, c->plen_buf, s));
-  DecoderArgs a;
-  a.N = N; a.steps = steps; a.E = E; a.heads = c->cfg.dec_heads; a.layers = c->cfg.dec_layers; a.vocab = c->cfg.dec_vocab;
-  a.prefix_size = c->cfg.prefix_size; a.eps = c->cfg.dec_ln_eps; a.prefix = nullptr; a.clip_w = nullptr; a.clip_b = nullptr;
-  a.wte = c->wte; a.wpe = c->wpe; a.head_w = c->head_w; a.head_c = c->head_c; a.head_d = c->head_d; a.layer = c->dl.data();
-  a.x = c->dx; a.qkv = c->dqkv; a.att = c->datt; a.hid = c->dhid; a.splitk_ws = c->splitk_ws; a.splitk_cnt = c->splitk_cnt; a.lm_tail = 0;
-  a.kcache = c->kcache; a.vcache = c->vcache; a.max_steps = c->cfg.max_steps; a.logits = c->logits; a.ids = c->ids_buf; a.logprob = nullptr;
-  a.head_w16 = c->head_w16; a.head_w16_unscale = c->head_w16_unscale; a.head_bound_coef = c->head_bound_coef;
-  a.xh = c->dec_xh; a.lm_stats = c->lm_stats; a.lm_gmax = c->lm_gmax; a.pos_base = 0;
-  a.pre_x = c->pre_x; a.pre_qkv = c->pre_qkv; a.pre_att = c->pre_att; a.pre_hid = c->pre_hid; a.pre_rows = pio_context::kPrefillRows;
+  DecoderArgs a = lm_args(c, N, steps);                        // (lm_tail is off: refused above)
+  with_prefill(a, c);
   HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
   const int32_t* plen = c->plen_buf;
   const int split = c->batched_prefill ? 16 : 256;      // the prompt lengths pio_viecap_decode prefills on one row group (decoder.hip)
   if (c->use_graph) {
-    if ((rc = launch_prompted_graph(c, pio_context::PKey{N, Pmax, steps, 1},
+    if ((rc = launch_prompted_graph(c, pio_context::PKey{pio_context::RAGGED, N, Pmax, steps},
                                     [&](hipStream_t cs) { return launch_decode_prompted_ragged(a, c->prompt_buf, Pmax, plen, split, cs); }, s)))
       return rc;
   } else {
@@ -1811,9 +1793,8 @@ int pio_lm_beam_search(pio_handle c, const float* embeds, const int32_t* plen, i
   int rc;
   if ((rc = prompted_workspaces(c, true))) return rc;          // the batched prefill workspace (allocated once per handle)
   const int R = N * W, Rc = cap, S = c->cfg.max_steps;
-  DecoderArgs a = lm_args(c, R);
-  a.steps = steps;
-  a.pre_x = c->pre_x; a.pre_qkv = c->pre_qkv; a.pre_att = c->pre_att; a.pre_hid = c->pre_hid; a.pre_rows = pio_context::kPrefillRows;
+  DecoderArgs a = lm_args(c, R, steps);
+  with_prefill(a, c);
   BeamArgs b;
   // a captured graph reads the handle's buffers only: the prompts and their lengths are copied in, the results out
   const size_t E = c->cfg.dec_embd;
@@ -1829,10 +1810,8 @@ int pio_lm_beam_search(pio_handle c, const float* embeds, const int32_t* plen, i
   b.tab = c->bs_i + 6 * Rc; b.hist = c->bs_i + (size_t)6 * Rc + (size_t)Rc * S;
   HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
   if (c->use_graph) {
-    // graphs keyed on (N, Pmax, steps), W, whether plen is given (PKey::ragged = 16 + W (+ 16 without plen): apart from the prompted
-    // decodes' 0 / 1) and the eos ids; the lengths themselves are read from the device
-    if ((rc = launch_prompted_graph(c, pio_context::PKey{N, Pmax, steps, 16 + W + (plen ? 0 : 16), eos0, eos1}, [&](hipStream_t cs) { return launch_lm_beam_search(a, b, cs); }, s)))
-      return rc;
+    const pio_context::PKey key{pio_context::BEAM, N, Pmax, steps, W, plen ? 1 : 0, eos0, eos1};
+    if ((rc = launch_prompted_graph(c, key, [&](hipStream_t cs) { return launch_lm_beam_search(a, b, cs); }, s))) return rc;
   } else {
     HIP_OK(launch_lm_beam_search(a, b, s));
   }
@@ -1906,22 +1885,20 @@ int pio_lm_sample(pio_handle c, const float* embeds, int32_t N, int32_t P, int32
     if ((rc = c->dmalloc(&c->smp_i, (size_t)cap * 2))) return rc;
   }
   const size_t E = c->cfg.dec_embd;
-  DecoderArgs a = lm_args(c, N);
-  a.steps = steps; a.pos_base = P - 1;
-  if (c->batched_prefill) { a.pre_x = c->pre_x; a.pre_qkv = c->pre_qkv; a.pre_att = c->pre_att; a.pre_hid = c->pre_hid; a.pre_rows = pio_context::kPrefillRows; }
+  DecoderArgs a = lm_args(c, N, steps, P - 1);
+  if (c->batched_prefill) with_prefill(a, c);
   // a captured graph reads the handle's buffers only: the prompt and the uniforms are brought in, the results copied out
   HIP_OK(hipMemcpyAsync(c->prompt_buf, embeds, (size_t)N * P * E * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (uniforms) HIP_OK(hipMemcpyAsync(c->smp_u, uniforms, (size_t)N * steps * sizeof(float), hipMemcpyDeviceToDevice, s));
   else HIP_OK(launch_philox_uniforms(seed, N, steps, c->smp_u, s));
   HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
   int32_t *active = c->smp_i, *lens_buf = c->smp_i + cap;
-  int32_t tbits, pbits;                                     // temperature, top_p and stop_id are kernel arguments of the graph: part of its key
-  memcpy(&tbits, &temperature, 4); memcpy(&pbits, &top_p, 4);
   auto launch = [&](hipStream_t cs) { return launch_lm_sample(a, c->prompt_buf, P, temperature, top_p, stop_id, c->smp_u, active, c->bs_f, lens_buf, cs); };
   if (c->use_graph) {
-    // PKey::ragged = 64 + stop_id (apart from the prompted decodes' 0 / 1 and the beam search's 17 .. 40); eos0 / eos1 carry the bits of
-    // temperature and top_p
-    if ((rc = launch_prompted_graph(c, pio_context::PKey{N, P, steps, 64 + stop_id, tbits, pbits}, launch, s))) return rc;
+    pio_context::PKey key{pio_context::SAMPLE, N, P, steps};   // temperature, top_p and stop_id are kernel arguments of the graph
+    key.stop_id = stop_id;
+    memcpy(&key.temp_bits, &temperature, 4); memcpy(&key.top_p_bits, &top_p, 4);
+    if ((rc = launch_prompted_graph(c, key, launch, s))) return rc;
   } else {
     HIP_OK(launch(s));
   }

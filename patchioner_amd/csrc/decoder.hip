@@ -414,8 +414,8 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? PIO_DEC_GEMM_WAVES : 1) void k
 //            pass are in flight at once; 3 shuffles finish the dot product.
 //   output : thread (c4 = tid % (hd/4), jg = tid / (hd/4)) accumulates 4 channels over keys j = jg (mod NJ);
 //            the NJ partial sums meet in LDS.
-// grid.y > 1 (batched prompt prefill, dec_prefill_layers): workgroup (x, y) handles position pos0 + y of prefix n, whose activations are
-// row n * rows_per_n + y of qkv / att; the keys and values of ALL those positions have been appended by k_kv_append before the launch
+// grid.y > 1 (batched prompt prefill, dec_prompt_prefill): workgroup (x, y) handles position pos0 + y of prefix n, whose activations are
+// row n * rows_per_n + y of qkv / att; the keys and values of ALL those positions have been appended by k_kv_append_masked before the launch
 // (the workgroup's own append below then rewrites the values that are there).  Same loads, same order per (prefix, head, position).
 // RAG (ragged prompted decode, grid.y == 1): prefix n's new position is plen[n] + pos0 (its own prompt length plus the step), read from
 // device memory; the loop bodies are the uniform kernel's, so a row attends over its keys exactly as the uniform kernel does for that count.
@@ -1220,13 +1220,39 @@ static hipError_t dec_gemm_s_launch(const void* Ws, float unscale, const float* 
   return hipGetLastError();
 }
 
-// K = 768 (4 waves x 12 chunks), 512 (4 x 8) or 3072 (4 workgroups x 4 waves x 12, split-K with `ws` / `cnt`)
+// The tile table of k_dec_gemm_b: <RGB, NCG, KS> by the rows and columns of a launch (K = 768: qkv / fc at 48 or 32 columns per workgroup, proj at 16;
+// K = 3072: fc2, split-K over 4 slices).  Returns the launch's result, or DEC_GEMM_B_NO_TILE when the kernel has no tile for this shape and
+// nothing was launched (dec_gemm_b_launch itself never returns that code).
+constexpr hipError_t DEC_GEMM_B_NO_TILE = hipErrorNotSupported;
+template <int EPI, int LN>
+static hipError_t dec_gemm_b_tile(const float* W, const float* X, int N, int Nout, int K, const float* bias, float* out,
+                                  const float* cvec, float eps, float* ws, unsigned* cnt, hipStream_t s) {
+  const int rg = ceil_div(N, 16);
+#define PIO_DGB(R, C, KSV) dec_gemm_b_launch<R, C, KSV, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s)
+  if (K == 768 && Nout % 48 == 0) {
+    const bool wide = Nout >= 2304;
+    if (rg > 4) return wide ? PIO_DGB(2, 3, 1) : PIO_DGB(2, 1, 1);
+    if (rg > 2) return wide ? PIO_DGB(2, 2, 1) : PIO_DGB(1, 1, 1);
+    return wide ? PIO_DGB(1, 2, 1) : PIO_DGB(1, 1, 1);
+  }
+  if constexpr (EPI == DE_RESID && !LN) {
+    if (K == 3072 && Nout % 32 == 0 && Nout <= 1024 && ws != nullptr && cnt != nullptr) {
+      if (rg > 4) return PIO_DGB(4, 2, 4);
+      if (rg > 2) return PIO_DGB(2, 2, 4);
+      return PIO_DGB(1, 2, 4);
+    }
+  }
+#undef PIO_DGB
+  return DEC_GEMM_B_NO_TILE;
+}
+
 #ifndef PIO_DEC_SPLIT_NCG_FC    // column groups (of 16) per workgroup for c_fc / mlp.c_proj in the split-fp16 form
 #define PIO_DEC_SPLIT_NCG_FC 3
 #endif
 #ifndef PIO_DEC_SPLIT_MIN_RG    // 16-row groups from which the layer GEMMs take the split-fp16 form when the split weights exist (5: 65+ prefixes)
 #define PIO_DEC_SPLIT_MIN_RG 5
 #endif
+// K = 768 (4 waves x 12 chunks), 512 (4 x 8) or 3072 (4 workgroups x 4 waves x 12, split-K with `ws` / `cnt`)
 template <int EPI, int LN>
 static hipError_t dec_gemm(const float* W, const float* X, int N, int Nout, int K, const float* bias, float* out,
                            const float* extra, const float* cvec, float eps, float* ws, unsigned* cnt, hipStream_t s,
@@ -1255,22 +1281,9 @@ static hipError_t dec_gemm(const float* W, const float* X, int N, int Nout, int 
     }
   }
   if constexpr (PIO_DEC_TILED != 0 && (EPI == DE_STORE || EPI == DE_RESID || EPI == DE_GELU)) {
-    const int rg = ceil_div(N, 16);
-    if (rg >= 2 && K == 768 && Nout % 48 == 0) {
-      const bool wide = Nout >= 2304;       // qkv / fc: 48 (32) columns per workgroup; proj: 16
-      if (rg > 4) return wide ? dec_gemm_b_launch<2, 3, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s)
-                              : dec_gemm_b_launch<2, 1, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-      if (rg > 2) return wide ? dec_gemm_b_launch<2, 2, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s)
-                              : dec_gemm_b_launch<1, 1, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-      return wide ? dec_gemm_b_launch<1, 2, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s)
-                  : dec_gemm_b_launch<1, 1, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-    }
-    if constexpr (EPI == DE_RESID && !LN) {
-      if (rg >= 2 && K == 3072 && Nout % 32 == 0 && Nout <= 1024 && ws != nullptr && cnt != nullptr) {
-        if (rg > 4) return dec_gemm_b_launch<4, 2, 4, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-        if (rg > 2) return dec_gemm_b_launch<2, 2, 4, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-        return dec_gemm_b_launch<1, 2, 4, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-      }
+    if (N > 16) {      // <= 16 rows stay on k_dec_gemm; so does a shape the tiled kernel has no tile for
+      const hipError_t e = dec_gemm_b_tile<EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
+      if (e != DEC_GEMM_B_NO_TILE) return e;
     }
   }
   if (K == 768) return dec_gemm_rg<12, 1, EPI, LN>(W, X, N, Nout, K, bias, out, extra, cvec, eps, ws, cnt, s);
@@ -1300,23 +1313,8 @@ static hipError_t dec_gemm_cls(int cls, const float* W, const float* X, int N, i
   if (N < 1 || N > 128) return hipErrorInvalidValue;
   const int rg = ceil_div(N, 16);
   if (cls == DEC_CLS_B) {
-    if (K == 768 && Nout % 48 == 0) {
-      const bool wide = Nout >= 2304;
-      if (rg > 4) return wide ? dec_gemm_b_launch<2, 3, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s)
-                              : dec_gemm_b_launch<2, 1, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-      if (rg > 2) return wide ? dec_gemm_b_launch<2, 2, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s)
-                              : dec_gemm_b_launch<1, 1, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-      return wide ? dec_gemm_b_launch<1, 2, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s)
-                  : dec_gemm_b_launch<1, 1, 1, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-    }
-    if constexpr (EPI == DE_RESID && !LN) {
-      if (K == 3072 && Nout % 32 == 0 && Nout <= 1024 && ws != nullptr && cnt != nullptr) {
-        if (rg > 4) return dec_gemm_b_launch<4, 2, 4, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-        if (rg > 2) return dec_gemm_b_launch<2, 2, 4, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-        return dec_gemm_b_launch<1, 2, 4, EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
-      }
-    }
-    return hipErrorInvalidValue;
+    const hipError_t e = dec_gemm_b_tile<EPI, LN>(W, X, N, Nout, K, bias, out, cvec, eps, ws, cnt, s);
+    return e == DEC_GEMM_B_NO_TILE ? hipErrorInvalidValue : e;
   }
   const int KS = K == 768 ? 1 : (K == 3072 ? 4 : 0);
   if (KS == 0 || (KS == 4 && (EPI != DE_RESID || LN || ws == nullptr || cnt == nullptr || Nout > 1024))) return hipErrorInvalidValue;
@@ -1330,8 +1328,6 @@ static hipError_t dec_gemm_cls(int cls, const float* W, const float* X, int N, i
 #undef PIO_DGA
   return hipGetLastError();
 }
-
-hipError_t decoder_init() { return hipSuccess; }   // no function attributes needed any more
 
 #define PIO_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
 
@@ -2028,34 +2024,70 @@ hipError_t launch_lmhead(const float* W, const float* X, int N, int V, int E, co
   return dec_gemm<DE_ARGMAX, 1>(W, X, N, V, E, dvec, part, nullptr, cvec, eps, nullptr, nullptr, s);
 }
 
+// ---- the layer pass ------------------------------------------------------------------------------------------------------------
+// A transformer layer is five launches: qkv GEMM, attention, attn.c_proj, c_fc, mlp.c_proj.  Which GEMM launcher they name is part of the
+// bit contract: the kernels sum a row in different orders (see dec_gemm_cls), so "row n of a ragged decode equals the uniform decode of
+// that row alone" and "batched beams equal per-image beams" hold only while every call site keeps its line of this table:
+//
+//   call site                                              | selector         | GEMMs                         | split-fp16 weights
+//   -------------------------------------------------------+------------------+-------------------------------+----------------------------
+//   uniform step (greedy, prompted, lm_score, lm_prefill,  | DG_BY_ROWS_SPLIT | dec_gemm, chosen by row count | passed for attn / fc / fc2,
+//     lm_advance, sampling, position-by-position prompt)   |                  |   (all rows in one launch)    |   never for proj
+//   uniform batched prefill (prompted, sampling)           | DG_BY_ROWS       | dec_gemm per 128-row chunk    | NOT passed
+//   ragged step, beam step                                 | DG_FAMILY_A      | family A on all rows          | none
+//   ragged prefill pass 1; beam prefill (split = 1 << 30,  | DG_FAMILY_A,     | family A per 128-row chunk    | none
+//     cache row stride W)                                  |   mask 1         |                               |
+//   ragged prefill pass 2                                  | DG_FAMILY_B,     | family B per 128-row chunk    | none
+//                                                          |   mask 2         |                               |
+//
+// On every line mlp.c_proj (fc2), and no other GEMM, gets the split-K workspace a.splitk_ws / a.splitk_cnt.
+enum DecGemms { DG_FAMILY_A = DEC_CLS_A, DG_FAMILY_B = DEC_CLS_B, DG_BY_ROWS = 2, DG_BY_ROWS_SPLIT = 3 };
+
+// One GEMM of a layer over `rows` rows, by the table above.
+template <int EPI, int LN>
+static hipError_t dec_layer_gemm(DecGemms g, const float* W, const float* X, int rows, int Nout, int K, const float* bias, float* out,
+                                 const float* cvec, float eps, float* ws, unsigned* cnt, const void* Wsplit, float unscale, hipStream_t s) {
+  const int chunk = g == DG_BY_ROWS_SPLIT ? rows : 128;
+  for (int r0 = 0; r0 < rows; r0 += chunk) {
+    const int n = rows - r0 < chunk ? rows - r0 : chunk;
+    const float* x = X + (size_t)r0 * K;
+    float* o = out + (size_t)r0 * Nout;
+    if (g == DG_FAMILY_A || g == DG_FAMILY_B) PIO_TRY((dec_gemm_cls<EPI, LN>(g, W, x, n, Nout, K, bias, o, cvec, eps, ws, cnt, s)));
+    else PIO_TRY((dec_gemm<EPI, LN>(W, x, n, Nout, K, bias, o, nullptr, cvec, eps, ws, cnt, s, g == DG_BY_ROWS_SPLIT ? Wsplit : nullptr, unscale)));
+  }
+  return hipSuccess;
+}
+
+// Every layer over `rows` rows of x / qkv / att / hid (x in place).  attn(kc, vc) launches one layer's attention, and whatever fills the
+// cache before it; that layer's keys / values start at row crow0 of the cache [layers][a.N][max_steps][E].
+template <class Attn>
+static hipError_t dec_layers(const DecoderArgs& a, DecGemms g, float* x, float* qkv, float* att, float* hid, int rows, size_t crow0, Attn attn,
+                             hipStream_t s) {
+  const int E = a.E;
+  for (int l = 0; l < a.layers; ++l) {
+    const DecLayerW& w = a.layer[l];
+    const size_t coff = ((size_t)l * a.N + crow0) * a.max_steps * E;
+    PIO_TRY((dec_layer_gemm<DE_STORE, 1>(g, w.attn_w, x, rows, 3 * E, E, w.attn_d, qkv, w.attn_c, a.eps, nullptr, nullptr, w.attn_ws, w.attn_un, s)));
+    attn(a.kcache + coff, a.vcache + coff);
+    PIO_TRY((dec_layer_gemm<DE_RESID, 0>(g, w.proj_w, att, rows, E, E, w.proj_b, x, nullptr, 0.f, nullptr, nullptr, nullptr, 0.f, s)));
+    PIO_TRY((dec_layer_gemm<DE_GELU, 1>(g, w.fc_w, x, rows, 4 * E, E, w.fc_d, hid, w.fc_c, a.eps, nullptr, nullptr, w.fc_ws, w.fc_un, s)));
+    PIO_TRY((dec_layer_gemm<DE_RESID, 0>(g, w.fc2_w, hid, rows, E, 4 * E, w.fc2_b, x, nullptr, 0.f, a.splitk_ws, a.splitk_cnt, w.fc2_ws, w.fc2_un, s)));
+  }
+  return hipGetLastError();
+}
+
 // One new position `pos` of every prefix through the transformer layers (x in place; keys / values appended at `pos`).
 // RAG: prefix n's position is plen[n] + pos.  tab (RAG only; batched beam search): the history of row n is read through tab [N][a.max_steps].
 template <bool RAG = false>
 static hipError_t dec_layers_step(const DecoderArgs& a, int pos, hipStream_t s, const int32_t* plen = nullptr, const int32_t* tab = nullptr) {
-  const int N = a.N, E = a.E;
-  for (int l = 0; l < a.layers; ++l) {
-    const DecLayerW& w = a.layer[l];
-    float* kc = a.kcache + (size_t)l * N * a.max_steps * E;
-    float* vc = a.vcache + (size_t)l * N * a.max_steps * E;
-    if constexpr (RAG) {             // every row on the kernels of a one-row decode, whatever the rows of the launch (dec_gemm_cls)
-      PIO_TRY((dec_gemm_cls<DE_STORE, 1>(DEC_CLS_A, w.attn_w, a.x, N, 3 * E, E, w.attn_d, a.qkv, w.attn_c, a.eps, nullptr, nullptr, s)));
-      if (tab != nullptr)
-        hipLaunchKernelGGL((k_dec_attention<true, 0, true>), dim3(N * a.heads), dim3(256), 0, s, a.qkv, kc, vc, E, a.heads, pos, a.max_steps, a.att, 1,
-                           plen, 0, tab, a.max_steps);
-      else
-        hipLaunchKernelGGL(k_dec_attention<true>, dim3(N * a.heads), dim3(256), 0, s, a.qkv, kc, vc, E, a.heads, pos, a.max_steps, a.att, 1, plen, 0);
-      PIO_TRY((dec_gemm_cls<DE_RESID, 0>(DEC_CLS_A, w.proj_w, a.att, N, E, E, w.proj_b, a.x, nullptr, 0.f, nullptr, nullptr, s)));
-      PIO_TRY((dec_gemm_cls<DE_GELU, 1>(DEC_CLS_A, w.fc_w, a.x, N, 4 * E, E, w.fc_d, a.hid, w.fc_c, a.eps, nullptr, nullptr, s)));
-      PIO_TRY((dec_gemm_cls<DE_RESID, 0>(DEC_CLS_A, w.fc2_w, a.hid, N, E, 4 * E, w.fc2_b, a.x, nullptr, 0.f, a.splitk_ws, a.splitk_cnt, s)));
-      continue;
-    }
-    PIO_TRY((dec_gemm<DE_STORE, 1>(w.attn_w, a.x, N, 3 * E, E, w.attn_d, a.qkv, nullptr, w.attn_c, a.eps, nullptr, nullptr, s, w.attn_ws, w.attn_un)));
-    hipLaunchKernelGGL(k_dec_attention<false>, dim3(N * a.heads), dim3(256), 0, s, a.qkv, kc, vc, E, a.heads, pos, a.max_steps, a.att, 1, nullptr, 0);
-    PIO_TRY((dec_gemm<DE_RESID, 0>(w.proj_w, a.att, N, E, E, w.proj_b, a.x, nullptr, nullptr, 0.f, nullptr, nullptr, s)));
-    PIO_TRY((dec_gemm<DE_GELU, 1>(w.fc_w, a.x, N, 4 * E, E, w.fc_d, a.hid, nullptr, w.fc_c, a.eps, nullptr, nullptr, s, w.fc_ws, w.fc_un)));
-    PIO_TRY((dec_gemm<DE_RESID, 0>(w.fc2_w, a.hid, N, E, 4 * E, w.fc2_b, a.x, nullptr, nullptr, 0.f, a.splitk_ws, a.splitk_cnt, s, w.fc2_ws, w.fc2_un)));
-  }
-  return hipSuccess;
+  const dim3 grid(a.N * a.heads);
+  return dec_layers(a, RAG ? DG_FAMILY_A : DG_BY_ROWS_SPLIT, a.x, a.qkv, a.att, a.hid, a.N, 0, [&](float* kc, float* vc) {
+    if (RAG && tab != nullptr)
+      hipLaunchKernelGGL((k_dec_attention<true, 0, true>), grid, dim3(256), 0, s, a.qkv, kc, vc, a.E, a.heads, pos, a.max_steps, a.att, 1, plen, 0,
+                         tab, a.max_steps);
+    else
+      hipLaunchKernelGGL(k_dec_attention<RAG>, grid, dim3(256), 0, s, a.qkv, kc, vc, a.E, a.heads, pos, a.max_steps, a.att, 1, plen, 0);
+  }, s);
 }
 
 // LM head on x -> ids[.][step] (+ log-prob) and the next position's input x = wte[id] + wpe[pos_base + step + 1]
@@ -2096,19 +2128,15 @@ __global__ __launch_bounds__(256) void k_dec_prompt_x(const float* __restrict__ 
   for (int d = threadIdx.x; d < E; d += 256) x[(size_t)n * E + d] = prompt[((size_t)n * P + pos) * E + d] + wpe[(size_t)pos * E + d];
 }
 
-// greedy_search of the ViECap head (P/src/viecap/search.py:108-191) with a KV cache: the prompt embeddings [N][P][E]
-// (soft + hard prompt, padded rows included: the reference uses no attention mask) occupy positions 0..P-1; the token
-// chosen from the logits of position P-1+k is ids[.][k] and becomes position P+k.  The reference's 64 iterations run
-// the prompt forward plus 64 single-token forwards and never use the logits of the last one: P + steps - 1 positions here.
-// a.pos_base must be P - 1.
 // ---- teacher-forced scoring: GPT2LMHeadModel(input_ids, labels = input_ids).loss as VieCap.compute_perplexity takes it
 // (P/src/viecap/entrypoint.py:155-172): the tokens of a finished caption go through the KV-cached layers position by
 // position; after position p the exact head gives log sum exp over the vocabulary (the partials of k_lmhead_wide) and one
 // more dot product the logit of the NEXT token; nll[n] accumulates their difference for p + 1 < lens[n].
-__global__ __launch_bounds__(256) void k_dec_token_x(const int32_t* __restrict__ tokens, int Lmax, int pos, const float* __restrict__ wte,
+// x[n][:] = wte[clamp(tokens[n * stride + col])][:] + wpe[pos][:]
+__global__ __launch_bounds__(256) void k_dec_token_x(const int32_t* __restrict__ tokens, int stride, int col, int pos, const float* __restrict__ wte,
                                                      const float* __restrict__ wpe, int E, int V, float* x) {
   const int n = blockIdx.x;
-  int t = tokens[(size_t)n * Lmax + pos];
+  int t = tokens[(size_t)n * stride + col];
   t = t < 0 ? 0 : (t >= V ? V - 1 : t);
   for (int d = threadIdx.x; d < E; d += 256) x[(size_t)n * E + d] = wte[(size_t)t * E + d] + wpe[(size_t)pos * E + d];
 }
@@ -2166,7 +2194,7 @@ hipError_t launch_lm_score(const DecoderArgs& a, const int32_t* tokens, const in
   if (a.N < 1 || a.N > 64 || Lmax < 1 || Lmax > a.max_steps || !dec_args_ok(a, false, Lmax)) return hipErrorInvalidValue;
   PIO_TRY(hipMemsetAsync(nll, 0, (size_t)a.N * sizeof(float), s));
   for (int pos = 0; pos + 1 < Lmax; ++pos) {
-    hipLaunchKernelGGL(k_dec_token_x, dim3(a.N), dim3(256), 0, s, tokens, Lmax, pos, a.wte, a.wpe, a.E, a.vocab, a.x);
+    hipLaunchKernelGGL(k_dec_token_x, dim3(a.N), dim3(256), 0, s, tokens, Lmax, pos, pos, a.wte, a.wpe, a.E, a.vocab, a.x);
     PIO_TRY(dec_layers_step(a, pos, s));
     int nblk = 0;
     PIO_TRY(launch_lmhead(a.head_w, a.x, a.N, a.vocab, a.E, a.head_d, a.head_c, a.eps, a.logits, &nblk, s));
@@ -2180,7 +2208,7 @@ hipError_t launch_lm_score(const DecoderArgs& a, const int32_t* tokens, const in
 // value cache, so the layer GEMMs take all N * P rows at once (128 rows per launch on the exact fp32 kernels: no split-fp16 operands here)
 // instead of P passes over N rows: per layer ceil(N P / 128) * 4 + 2 launches instead of 5 P (config 5: 16 prefixes x ~30 prompt
 // positions x 12 layers = 1 800 launches of the 5 600 a ViECap caption batch took).  Rows are [n][p]; the attention of position p reads
-// the cache, which k_kv_append fills for every position first.  The sums of a GEMM row are those of k_dec_gemm_b instead of k_dec_gemm
+// the cache, which k_kv_append_masked fills for every position first.  The sums of a GEMM row are those of k_dec_gemm_b instead of k_dec_gemm
 // (another order of the same exact fp32 products: rounding-level differences in the cache, ids held to the reference's fixtures by
 // tests/test_gpu_viecap.py).
 __global__ __launch_bounds__(256) void k_dec_prompt_x_all(const float* __restrict__ prompt, const float* __restrict__ wpe, int P, int E, float* x) {
@@ -2188,74 +2216,6 @@ __global__ __launch_bounds__(256) void k_dec_prompt_x_all(const float* __restric
   const size_t r = (size_t)n * P + p;
   for (int d = threadIdx.x; d < E; d += 256) x[r * E + d] = prompt[r * E + d] + wpe[(size_t)p * E + d];
 }
-__global__ __launch_bounds__(192) void k_kv_append(const float* __restrict__ qkv, float* kcache, float* vcache, int P, int max_steps, int E) {
-  const int n = blockIdx.x, p = blockIdx.y;
-  const float4* src = (const float4*)(qkv + ((size_t)n * P + p) * 3 * E);
-  float4* kc = (float4*)(kcache + ((size_t)n * max_steps + p) * E);
-  float4* vc = (float4*)(vcache + ((size_t)n * max_steps + p) * E);
-  for (int d = threadIdx.x; d < E / 4; d += 192) { kc[d] = src[E / 4 + d]; vc[d] = src[E / 2 + d]; }
-}
-__global__ __launch_bounds__(256) void k_dec_last_rows(const float* __restrict__ xp, int P, int E, float* x) {
-  const int n = blockIdx.x;
-  for (int d = threadIdx.x; d < E; d += 256) x[(size_t)n * E + d] = xp[((size_t)n * P + P - 1) * E + d];
-}
-static hipError_t dec_prefill_layers(const DecoderArgs& a, int n0, int gN, int P, hipStream_t s) {
-  const int E = a.E, R = gN * P;
-  for (int l = 0; l < a.layers; ++l) {
-    const DecLayerW& w = a.layer[l];
-    float* kc = a.kcache + ((size_t)l * a.N + n0) * a.max_steps * E;
-    float* vc = a.vcache + ((size_t)l * a.N + n0) * a.max_steps * E;
-    for (int r0 = 0; r0 < R; r0 += 128) {
-      const int rows = R - r0 < 128 ? R - r0 : 128;
-      PIO_TRY((dec_gemm<DE_STORE, 1>(w.attn_w, a.pre_x + (size_t)r0 * E, rows, 3 * E, E, w.attn_d, a.pre_qkv + (size_t)r0 * 3 * E, nullptr, w.attn_c,
-                                     a.eps, nullptr, nullptr, s)));
-    }
-    hipLaunchKernelGGL(k_kv_append, dim3(gN, P), dim3(192), 0, s, a.pre_qkv, kc, vc, P, a.max_steps, E);
-    hipLaunchKernelGGL((k_dec_attention<false, 0>), dim3(gN * a.heads, P), dim3(256), 0, s, a.pre_qkv, kc, vc, E, a.heads, 0, a.max_steps, a.pre_att, P,
-                       nullptr, 0);
-    for (int r0 = 0; r0 < R; r0 += 128) {
-      const int rows = R - r0 < 128 ? R - r0 : 128;
-      PIO_TRY((dec_gemm<DE_RESID, 0>(w.proj_w, a.pre_att + (size_t)r0 * E, rows, E, E, w.proj_b, a.pre_x + (size_t)r0 * E, nullptr, nullptr, 0.f,
-                                     nullptr, nullptr, s)));
-    }
-    for (int r0 = 0; r0 < R; r0 += 128) {
-      const int rows = R - r0 < 128 ? R - r0 : 128;
-      PIO_TRY((dec_gemm<DE_GELU, 1>(w.fc_w, a.pre_x + (size_t)r0 * E, rows, 4 * E, E, w.fc_d, a.pre_hid + (size_t)r0 * 4 * E, nullptr, w.fc_c, a.eps,
-                                    nullptr, nullptr, s)));
-    }
-    for (int r0 = 0; r0 < R; r0 += 128) {
-      const int rows = R - r0 < 128 ? R - r0 : 128;
-      PIO_TRY((dec_gemm<DE_RESID, 0>(w.fc2_w, a.pre_hid + (size_t)r0 * 4 * E, rows, E, 4 * E, w.fc2_b, a.pre_x + (size_t)r0 * E, nullptr, nullptr, 0.f,
-                                     a.splitk_ws, a.splitk_cnt, s)));
-    }
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_decode_prompted(const DecoderArgs& a, const float* prompt, int P, hipStream_t s) {
-  const bool filtered = PIO_LMHEAD_FILTER && a.logprob == nullptr && a.head_w16 != nullptr;
-  if (P < 1 || a.steps < 1 || a.pos_base != P - 1 || !dec_args_ok(a, filtered, P + a.steps - 1)) return hipErrorInvalidValue;
-  if (a.pre_x != nullptr && P > 1 && P <= a.pre_rows) {
-    const int gmax = a.pre_rows / P;                  // prefixes whose prompts fit the prefill workspace at once
-    for (int n0 = 0; n0 < a.N; n0 += gmax) {
-      const int gN = a.N - n0 < gmax ? a.N - n0 : gmax;
-      hipLaunchKernelGGL(k_dec_prompt_x_all, dim3(gN, P), dim3(256), 0, s, prompt + (size_t)n0 * P * a.E, a.wpe, P, a.E, a.pre_x);
-      PIO_TRY(dec_prefill_layers(a, n0, gN, P, s));
-      hipLaunchKernelGGL(k_dec_last_rows, dim3(gN), dim3(256), 0, s, a.pre_x, P, a.E, a.x + (size_t)n0 * a.E);
-    }
-  } else {
-    for (int pos = 0; pos < P; ++pos) {
-      hipLaunchKernelGGL(k_dec_prompt_x, dim3(a.N), dim3(256), 0, s, prompt, a.wpe, P, pos, a.E, a.x);
-      PIO_TRY(dec_layers_step(a, pos, s));
-    }
-  }
-  for (int step = 0; step < a.steps; ++step) {
-    PIO_TRY(dec_head_step(a, step, filtered, s));            // -> ids[.][step], x = wte[id] + wpe[P + step]
-    if (step + 1 < a.steps) PIO_TRY(dec_layers_step(a, P + step, s));
-  }
-  return hipGetLastError();
-}
-
 // ---- ragged prompted decode: prefix n has its own prompt length P_n = plen[n] (device memory, 1 <= P_n <= Pmax).  Everything the
 // host sees is (N, Pmax, steps), so one captured graph serves any mix of lengths.  The prompt rows are laid out at Pmax per prefix
 // (positions >= P_n: zeros, k_build_prompt_ragged) and prefilled like a uniform prompt of Pmax positions: causal attention keeps
@@ -2263,13 +2223,15 @@ hipError_t launch_decode_prompted(const DecoderArgs& a, const float* prompt, int
 // P_n + k before any later step reads that slot (step k attends over slots 0 .. P_n + k, the last one being its own fresh key).  The
 // input of the first step is the prefill output of position P_n - 1; step k runs position P_n + k (k_dec_attention<true>) and the
 // head writes x = wte[id] + wpe[P_n + k] (k_dec_select*<true>).  The head is the uniform path's; the GEMMs: see launch_decode_prompted_ragged.
-// Pass `cls` of the ragged prefill writes keys / values (and the first step's input) only for its own prefixes: MASK 1 = plen[n] <= split
-// (family A), 2 = plen[n] > split (family B).
+// A pass of the ragged prefill writes keys / values (and the first step's input) only for its own prefixes: MASK 1 = plen[n] <= split
+// (family A), 2 = plen[n] > split (family B).  MASK 0 is the uniform prompt: every prefix, P positions each, plen not read.
 template <int MASK>
 __global__ __launch_bounds__(192) void k_kv_append_masked(const float* __restrict__ qkv, float* kcache, float* vcache, int P, int max_steps, int E,
                                                           const int32_t* __restrict__ plen, int split) {
   const int n = blockIdx.x, p = blockIdx.y;
-  if ((plen[n] <= split) != (MASK == 1)) return;          // block-uniform
+  if constexpr (MASK != 0) {
+    if ((plen[n] <= split) != (MASK == 1)) return;          // block-uniform
+  }
   const float4* src = (const float4*)(qkv + ((size_t)n * P + p) * 3 * E);
   float4* kc = (float4*)(kcache + ((size_t)n * max_steps + p) * E);
   float4* vc = (float4*)(vcache + ((size_t)n * max_steps + p) * E);
@@ -2279,57 +2241,63 @@ template <int MASK>
 __global__ __launch_bounds__(256) void k_dec_last_rows_ragged(const float* __restrict__ xp, int Pmax, const int32_t* __restrict__ plen, int split,
                                                               int E, float* x) {
   const int n = blockIdx.x;
-  if ((plen[n] <= split) != (MASK == 1)) return;
-  const size_t r = (size_t)n * Pmax + plen[n] - 1;
+  int last = Pmax;
+  if constexpr (MASK != 0) {
+    if ((plen[n] <= split) != (MASK == 1)) return;
+    last = plen[n];
+  }
+  const size_t r = (size_t)n * Pmax + last - 1;
   for (int d = threadIdx.x; d < E; d += 256) x[(size_t)n * E + d] = xp[r * E + d];
 }
-// dec_prefill_layers on one GEMM family (dec_gemm_cls), keys / values kept for the prefixes of that family only.
+
+// The prompts [N][P][E] of the first N prefixes through the layers: keys / values of the prompt positions into the cache, x[n] = the output
+// of prefix n's last prompt position.  The prefixes go in groups of a.pre_rows / P through the prefill workspace, all their positions as
+// the rows of one layer pass; the GEMMs and MASK follow the table above dec_layers.
+//   MASK 0 -- a uniform prompt of P positions.  Without the workspace (a.pre_x == null), at P == 1 or P > a.pre_rows the prompt goes position
+//             by position through the step kernels instead.
+//   MASK 1 / 2 -- one pass of a ragged prompt (P = Pmax, plen [N] on the device, split); the caller has checked the workspace.
 // rstride (batched beam search): prefix n's keys / values go to cache row n * rstride (the first beam of image n); the kernels see a row of
 // rstride * max_steps positions, of which the first max_steps are that cache row.
 template <int MASK>
-static hipError_t dec_prefill_layers_masked(const DecoderArgs& a, int n0, int gN, int P, const int32_t* plen, int split, hipStream_t s,
-                                            int rstride = 1) {
-  const int E = a.E, R = gN * P, cls = MASK == 1 ? DEC_CLS_A : DEC_CLS_B;
+static hipError_t dec_prompt_prefill(const DecoderArgs& a, int N, const float* prompt, int P, hipStream_t s, const int32_t* plen = nullptr,
+                                     int split = 0, int rstride = 1) {
+  const int E = a.E;
+  if (MASK == 0 && (a.pre_x == nullptr || P == 1 || P > a.pre_rows)) {
+    for (int pos = 0; pos < P; ++pos) {
+      hipLaunchKernelGGL(k_dec_prompt_x, dim3(N), dim3(256), 0, s, prompt, a.wpe, P, pos, E, a.x);
+      PIO_TRY(dec_layers_step(a, pos, s));
+    }
+    return hipGetLastError();
+  }
+  const DecGemms g = MASK == 0 ? DG_BY_ROWS : (MASK == 1 ? DG_FAMILY_A : DG_FAMILY_B);
+  const int gmax = a.pre_rows / P;                    // prefixes whose prompts fit the prefill workspace at once
   const int ms = a.max_steps * rstride;
-  for (int l = 0; l < a.layers; ++l) {
-    const DecLayerW& w = a.layer[l];
-    float* kc = a.kcache + ((size_t)l * a.N + (size_t)n0 * rstride) * a.max_steps * E;
-    float* vc = a.vcache + ((size_t)l * a.N + (size_t)n0 * rstride) * a.max_steps * E;
-    for (int r0 = 0; r0 < R; r0 += 128) {
-      const int rows = R - r0 < 128 ? R - r0 : 128;
-      PIO_TRY((dec_gemm_cls<DE_STORE, 1>(cls, w.attn_w, a.pre_x + (size_t)r0 * E, rows, 3 * E, E, w.attn_d, a.pre_qkv + (size_t)r0 * 3 * E, w.attn_c,
-                                         a.eps, nullptr, nullptr, s)));
-    }
-    hipLaunchKernelGGL(k_kv_append_masked<MASK>, dim3(gN, P), dim3(192), 0, s, a.pre_qkv, kc, vc, P, ms, E, plen, split);
-    hipLaunchKernelGGL((k_dec_attention<false, MASK>), dim3(gN * a.heads, P), dim3(256), 0, s, a.pre_qkv, kc, vc, E, a.heads, 0, ms, a.pre_att,
-                       P, plen, split);
-    for (int r0 = 0; r0 < R; r0 += 128) {
-      const int rows = R - r0 < 128 ? R - r0 : 128;
-      PIO_TRY((dec_gemm_cls<DE_RESID, 0>(cls, w.proj_w, a.pre_att + (size_t)r0 * E, rows, E, E, w.proj_b, a.pre_x + (size_t)r0 * E, nullptr, 0.f,
-                                         nullptr, nullptr, s)));
-    }
-    for (int r0 = 0; r0 < R; r0 += 128) {
-      const int rows = R - r0 < 128 ? R - r0 : 128;
-      PIO_TRY((dec_gemm_cls<DE_GELU, 1>(cls, w.fc_w, a.pre_x + (size_t)r0 * E, rows, 4 * E, E, w.fc_d, a.pre_hid + (size_t)r0 * 4 * E, w.fc_c, a.eps,
-                                        nullptr, nullptr, s)));
-    }
-    for (int r0 = 0; r0 < R; r0 += 128) {
-      const int rows = R - r0 < 128 ? R - r0 : 128;
-      PIO_TRY((dec_gemm_cls<DE_RESID, 0>(cls, w.fc2_w, a.pre_hid + (size_t)r0 * 4 * E, rows, E, 4 * E, w.fc2_b, a.pre_x + (size_t)r0 * E, nullptr, 0.f,
-                                         a.splitk_ws, a.splitk_cnt, s)));
-    }
+  for (int n0 = 0; n0 < N; n0 += gmax) {
+    const int gN = N - n0 < gmax ? N - n0 : gmax;
+    const int32_t* pl = MASK != 0 ? plen + n0 : nullptr;
+    hipLaunchKernelGGL(k_dec_prompt_x_all, dim3(gN, P), dim3(256), 0, s, prompt + (size_t)n0 * P * E, a.wpe, P, E, a.pre_x);
+    PIO_TRY(dec_layers(a, g, a.pre_x, a.pre_qkv, a.pre_att, a.pre_hid, gN * P, (size_t)n0 * rstride, [&](float* kc, float* vc) {
+      hipLaunchKernelGGL(k_kv_append_masked<MASK>, dim3(gN, P), dim3(192), 0, s, a.pre_qkv, kc, vc, P, ms, E, pl, split);
+      hipLaunchKernelGGL((k_dec_attention<false, MASK>), dim3(gN * a.heads, P), dim3(256), 0, s, a.pre_qkv, kc, vc, E, a.heads, 0, ms, a.pre_att, P,
+                         pl, split);
+    }, s));
+    hipLaunchKernelGGL(k_dec_last_rows_ragged<MASK>, dim3(gN), dim3(256), 0, s, a.pre_x, P, pl, split, E, a.x + (size_t)n0 * E);
   }
   return hipGetLastError();
 }
 
-template <int MASK>
-static hipError_t dec_prefill_ragged_pass(const DecoderArgs& a, const float* prompt, int Pmax, const int32_t* plen, int split, hipStream_t s) {
-  const int gmax = a.pre_rows / Pmax;
-  for (int n0 = 0; n0 < a.N; n0 += gmax) {
-    const int gN = a.N - n0 < gmax ? a.N - n0 : gmax;
-    hipLaunchKernelGGL(k_dec_prompt_x_all, dim3(gN, Pmax), dim3(256), 0, s, prompt + (size_t)n0 * Pmax * a.E, a.wpe, Pmax, a.E, a.pre_x);
-    PIO_TRY(dec_prefill_layers_masked<MASK>(a, n0, gN, Pmax, plen + n0, split, s));
-    hipLaunchKernelGGL(k_dec_last_rows_ragged<MASK>, dim3(gN), dim3(256), 0, s, a.pre_x, Pmax, plen + n0, split, a.E, a.x + (size_t)n0 * a.E);
+// greedy_search of the ViECap head (P/src/viecap/search.py:108-191) with a KV cache: the prompt embeddings [N][P][E]
+// (soft + hard prompt, padded rows included: the reference uses no attention mask) occupy positions 0..P-1; the token
+// chosen from the logits of position P-1+k is ids[.][k] and becomes position P+k.  The reference's 64 iterations run
+// the prompt forward plus 64 single-token forwards and never use the logits of the last one: P + steps - 1 positions here.
+// a.pos_base must be P - 1.
+hipError_t launch_decode_prompted(const DecoderArgs& a, const float* prompt, int P, hipStream_t s) {
+  const bool filtered = PIO_LMHEAD_FILTER && a.logprob == nullptr && a.head_w16 != nullptr;
+  if (P < 1 || a.steps < 1 || a.pos_base != P - 1 || !dec_args_ok(a, filtered, P + a.steps - 1)) return hipErrorInvalidValue;
+  PIO_TRY(dec_prompt_prefill<0>(a, a.N, prompt, P, s));
+  for (int step = 0; step < a.steps; ++step) {
+    PIO_TRY(dec_head_step(a, step, filtered, s));            // -> ids[.][step], x = wte[id] + wpe[P + step]
+    if (step + 1 < a.steps) PIO_TRY(dec_layers_step(a, P + step, s));
   }
   return hipGetLastError();
 }
@@ -2345,8 +2313,8 @@ hipError_t launch_decode_prompted_ragged(const DecoderArgs& a, const float* prom
   if (Pmax < 1 || Pmax > 128 || a.steps < 1 || plen == nullptr || a.lm_tail || a.pre_x == nullptr || Pmax > a.pre_rows || a.N > 128 ||
       !dec_args_ok(a, filtered, Pmax + a.steps - 1))
     return hipErrorInvalidValue;
-  PIO_TRY(dec_prefill_ragged_pass<1>(a, prompt, Pmax, plen, split, s));
-  if (Pmax > split) PIO_TRY(dec_prefill_ragged_pass<2>(a, prompt, Pmax, plen, split, s));
+  PIO_TRY(dec_prompt_prefill<1>(a, a.N, prompt, Pmax, s, plen, split));
+  if (Pmax > split) PIO_TRY(dec_prompt_prefill<2>(a, a.N, prompt, Pmax, s, plen, split));
   for (int step = 0; step < a.steps; ++step) {
     PIO_TRY(dec_head_step<true>(a, step, filtered, s, plen));          // -> ids[.][step], x = wte[id] + wpe[P_n + step]
     if (step + 1 < a.steps) PIO_TRY(dec_layers_step<true>(a, step, s, plen));
@@ -2357,15 +2325,6 @@ hipError_t launch_decode_prompted_ragged(const DecoderArgs& a, const float* prom
 // ---- beam search building blocks (ViECap: P/src/viecap/search.py:193-285; entrypoint.py:143-148 calls it per image with
 // beam_width beams).  The reference re-runs the whole sequence of every beam each step; here the beams keep KV caches that are
 // re-gathered by source beam after every selection.  None of this is on the benchmarked path: plain kernels.
-// x[n][:] = wte[tokens[n]][:] + wpe[pos][:]
-__global__ __launch_bounds__(256) void k_dec_token1_x(const int32_t* __restrict__ tokens, int pos, const float* __restrict__ wte,
-                                                      const float* __restrict__ wpe, int E, int V, float* x) {
-  const int n = blockIdx.x;
-  int t = tokens[n];
-  t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-  for (int d = threadIdx.x; d < E; d += 256) x[(size_t)n * E + d] = wte[(size_t)t * E + d] + wpe[(size_t)pos * E + d];
-}
-
 // dst[l][n][p][:] = src[l][rows ? rows[n] : n][p][:] for p < npos; grid (npos, N, layers)
 __global__ __launch_bounds__(192) void k_kv_gather(const float* __restrict__ src, float* __restrict__ dst, const int32_t* __restrict__ rows,
                                                    int N, int max_steps, int E) {
@@ -2489,63 +2448,6 @@ __global__ __launch_bounds__(1024) void k_beam_select(const float* __restrict__ 
   }
 }
 
-static hipError_t lm_logp_rows(const DecoderArgs& a, float* stats, float* logp, hipStream_t s) {
-  hipLaunchKernelGGL(k_row_stats, dim3(a.N), dim3(256), 0, s, a.x, a.E, a.eps, stats);
-  hipLaunchKernelGGL(k_lm_logits_full, dim3(ceil_div(a.vocab, 4)), dim3(256), 0, s, a.head_w, a.x, a.N, a.vocab, a.E, a.head_d, a.head_c,
-                     stats, logp);
-  hipLaunchKernelGGL(k_log_softmax_rows, dim3(a.N), dim3(1024), 0, s, logp, a.vocab);
-  return hipGetLastError();
-}
-
-// embeds [N][P][E] at positions 0..P-1 -> logp [N][V] = log softmax of the logits of position P-1
-hipError_t launch_lm_prefill(const DecoderArgs& a, const float* embeds, int P, float* stats, float* logp, hipStream_t s) {
-  if (P < 1 || a.N < 1 || a.N > 16 || !dec_args_ok(a, false, P)) return hipErrorInvalidValue;
-  for (int pos = 0; pos < P; ++pos) {
-    hipLaunchKernelGGL(k_dec_prompt_x, dim3(a.N), dim3(256), 0, s, embeds, a.wpe, P, pos, a.E, a.x);
-    PIO_TRY(dec_layers_step(a, pos, s));
-  }
-  return lm_logp_rows(a, stats, logp, s);
-}
-
-// beams re-ordered (KV rows of positions < pos gathered by src_rows through kv_scratch), then token[n] at position pos -> logp [N][V]
-hipError_t launch_lm_advance(const DecoderArgs& a, const int32_t* tokens, const int32_t* src_rows, int pos, float* kscratch,
-                             float* vscratch, float* stats, float* logp, hipStream_t s) {
-  if (pos < 1 || a.N < 1 || a.N > 16 || !dec_args_ok(a, false, pos + 1)) return hipErrorInvalidValue;
-  if (src_rows) {
-    const dim3 g(pos, a.N, a.layers);
-    hipLaunchKernelGGL(k_kv_gather, g, dim3(192), 0, s, a.kcache, kscratch, src_rows, a.N, a.max_steps, a.E);
-    hipLaunchKernelGGL(k_kv_gather, g, dim3(192), 0, s, a.vcache, vscratch, src_rows, a.N, a.max_steps, a.E);
-    hipLaunchKernelGGL(k_kv_gather, g, dim3(192), 0, s, kscratch, a.kcache, (const int32_t*)nullptr, a.N, a.max_steps, a.E);
-    hipLaunchKernelGGL(k_kv_gather, g, dim3(192), 0, s, vscratch, a.vcache, (const int32_t*)nullptr, a.N, a.max_steps, a.E);
-  }
-  hipLaunchKernelGGL(k_dec_token1_x, dim3(a.N), dim3(256), 0, s, tokens, pos, a.wte, a.wpe, a.E, a.vocab, a.x);
-  PIO_TRY(dec_layers_step(a, pos, s));
-  return lm_logp_rows(a, stats, logp, s);
-}
-
-hipError_t launch_beam_select(const float* logp, const float* scores, const float* lens, const int32_t* stopped, int W, int V,
-                              float* out_val, int64_t* out_idx, hipStream_t s) {
-  if (W < 1 || W > 8 || V < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_beam_select, dim3(1), dim3(1024), 0, s, logp, scores, lens, stopped, W, V, out_val, out_idx);
-  return hipGetLastError();
-}
-
-
-// ---- batched beam search (launch_lm_beam_search): N images x W beams as the rows of one decode, the bookkeeping on the device.
-// Bits: image n gets what VieCapHead.beam_search gives for it alone (pio_lm_prefill / pio_lm_advance / pio_beam_select + the host's fp32
-// bookkeeping), because every number goes through the same operations in the same order:
-//   prefill  -- the per-image path runs the prompt position by position on W identical rows, i.e. on k_dec_gemm (family A, <= 16 rows).
-//               Here the prompts of all images go through the batched prefill on family A (dec_gemm_cls: a row's sums do not depend on
-//               the launch) and the attention of a position keeps its reduction order (grid.y form: same loads per position);
-//               image n's keys / values land in cache row n W, which its W beams share through the table.
-//   steps    -- family A GEMMs on N W rows (dec_layers_step<true>) at row position P_n + i - 1, attention at that row's key count;
-//               the per-image path re-gathers the KV cache of its beams, here k_dec_attention<true, 0, true> reads position j of row r
-//               from cache row tab[r][j].  A row only ever writes its own slot at its current position, so no history is overwritten.
-//   head     -- k_row_stats, k_lm_logits_rows (k_lm_logits_full's sums, batched) and k_log_softmax_rows, one block per row.
-//   select   -- k_beam_step: per image the W largest candidates of k_beam_select's formula (a total order: value descending, flat index
-//               ascending, NaN never enters), then the host's bookkeeping in fp32, in its order; an image whose W beams have all
-//               stopped is frozen (the reference's break): nothing of its state changes any more.
-
 // out[n][v] = k_lm_logits_full's value for every row n < N and column v < V, reading each weight column once per launch: a wave keeps
 // BL_C columns of W in registers (lane l: d = l + 64 j) and walks all N rows.  Per (row, column): lane l's fmaf chain over j ascending,
 // wave_sum's tree, then rstd (acc - mu c) + d as two fmas -- the instructions hipcc emits for k_lm_logits_full's expression (fp-contract).
@@ -2591,6 +2493,65 @@ __global__ __launch_bounds__(256) void k_lm_logits_rows(const float* __restrict_
     for (int j = 0; j < J; ++j) xa[j] = xb[j];
   }
 }
+
+// The full-vocabulary head on the first `rows` rows of a.x: k_row_stats, every logit (LOGITS_FULL: k_lm_logits_full, LOGITS_ROWS: k_lm_logits_rows --
+// the same values, each caller keeps its kernel), then log softmax in place if asked.  stats: [rows][2] scratch; out [rows][V].
+enum LmLogits { LOGITS_FULL, LOGITS_ROWS };
+static hipError_t lm_head_rows(const DecoderArgs& a, int rows, LmLogits kind, bool log_softmax, float* stats, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_row_stats, dim3(rows), dim3(256), 0, s, a.x, a.E, a.eps, stats);
+  if (kind == LOGITS_FULL)
+    hipLaunchKernelGGL(k_lm_logits_full, dim3(ceil_div(a.vocab, 4)), dim3(256), 0, s, a.head_w, a.x, rows, a.vocab, a.E, a.head_d, a.head_c, stats, out);
+  else
+    hipLaunchKernelGGL(k_lm_logits_rows, dim3(ceil_div(a.vocab, 4 * BL_C)), dim3(256), 0, s, a.head_w, a.x, rows, a.vocab, a.head_d, a.head_c, stats, out);
+  if (log_softmax) hipLaunchKernelGGL(k_log_softmax_rows, dim3(rows), dim3(1024), 0, s, out, a.vocab);
+  return hipGetLastError();
+}
+
+// embeds [N][P][E] at positions 0..P-1 -> logp [N][V] = log softmax of the logits of position P-1
+hipError_t launch_lm_prefill(const DecoderArgs& a, const float* embeds, int P, float* stats, float* logp, hipStream_t s) {
+  if (P < 1 || a.N < 1 || a.N > 16 || !dec_args_ok(a, false, P)) return hipErrorInvalidValue;
+  PIO_TRY(dec_prompt_prefill<0>(a, a.N, embeds, P, s));
+  return lm_head_rows(a, a.N, LOGITS_FULL, true, stats, logp, s);
+}
+
+// beams re-ordered (KV rows of positions < pos gathered by src_rows through kv_scratch), then token[n] at position pos -> logp [N][V]
+hipError_t launch_lm_advance(const DecoderArgs& a, const int32_t* tokens, const int32_t* src_rows, int pos, float* kscratch,
+                             float* vscratch, float* stats, float* logp, hipStream_t s) {
+  if (pos < 1 || a.N < 1 || a.N > 16 || !dec_args_ok(a, false, pos + 1)) return hipErrorInvalidValue;
+  if (src_rows) {
+    const dim3 g(pos, a.N, a.layers);
+    hipLaunchKernelGGL(k_kv_gather, g, dim3(192), 0, s, a.kcache, kscratch, src_rows, a.N, a.max_steps, a.E);
+    hipLaunchKernelGGL(k_kv_gather, g, dim3(192), 0, s, a.vcache, vscratch, src_rows, a.N, a.max_steps, a.E);
+    hipLaunchKernelGGL(k_kv_gather, g, dim3(192), 0, s, kscratch, a.kcache, (const int32_t*)nullptr, a.N, a.max_steps, a.E);
+    hipLaunchKernelGGL(k_kv_gather, g, dim3(192), 0, s, vscratch, a.vcache, (const int32_t*)nullptr, a.N, a.max_steps, a.E);
+  }
+  hipLaunchKernelGGL(k_dec_token_x, dim3(a.N), dim3(256), 0, s, tokens, 1, 0, pos, a.wte, a.wpe, a.E, a.vocab, a.x);
+  PIO_TRY(dec_layers_step(a, pos, s));
+  return lm_head_rows(a, a.N, LOGITS_FULL, true, stats, logp, s);
+}
+
+hipError_t launch_beam_select(const float* logp, const float* scores, const float* lens, const int32_t* stopped, int W, int V,
+                              float* out_val, int64_t* out_idx, hipStream_t s) {
+  if (W < 1 || W > 8 || V < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_beam_select, dim3(1), dim3(1024), 0, s, logp, scores, lens, stopped, W, V, out_val, out_idx);
+  return hipGetLastError();
+}
+
+
+// ---- batched beam search (launch_lm_beam_search): N images x W beams as the rows of one decode, the bookkeeping on the device.
+// Bits: image n gets what VieCapHead.beam_search gives for it alone (pio_lm_prefill / pio_lm_advance / pio_beam_select + the host's fp32
+// bookkeeping), because every number goes through the same operations in the same order:
+//   prefill  -- the per-image path runs the prompt position by position on W identical rows, i.e. on k_dec_gemm (family A, <= 16 rows).
+//               Here the prompts of all images go through the batched prefill on family A (dec_gemm_cls: a row's sums do not depend on
+//               the launch) and the attention of a position keeps its reduction order (grid.y form: same loads per position);
+//               image n's keys / values land in cache row n W, which its W beams share through the table.
+//   steps    -- family A GEMMs on N W rows (dec_layers_step<true>) at row position P_n + i - 1, attention at that row's key count;
+//               the per-image path re-gathers the KV cache of its beams, here k_dec_attention<true, 0, true> reads position j of row r
+//               from cache row tab[r][j].  A row only ever writes its own slot at its current position, so no history is overwritten.
+//   head     -- k_row_stats, k_lm_logits_rows (k_lm_logits_full's sums, batched) and k_log_softmax_rows, one block per row.
+//   select   -- k_beam_step: per image the W largest candidates of k_beam_select's formula (a total order: value descending, flat index
+//               ascending, NaN never enters), then the host's bookkeeping in fp32, in its order; an image whose W beams have all
+//               stopped is frozen (the reference's break): nothing of its state changes any more.
 
 // k_beam_select's candidates of one image, from the rows lp[b][.] (b < rows): first (scores == null) lp[0][v]; otherwise stopped[b] ?
 // (v == 0 ? scores[b] / lens[b] : -inf) : (scores[b] + lp[b][v]) / (lens[b] + 1).  The W largest (value descending, flat index b V + v
@@ -2762,15 +2723,6 @@ __global__ __launch_bounds__(64) void k_beam_finish(const int32_t* __restrict__ 
   }
 }
 
-// logp[rows][V] = log softmax of the LM head on x's first `rows` rows
-static hipError_t beam_head(const DecoderArgs& a, int rows, float* stats, float* logp, hipStream_t s) {
-  hipLaunchKernelGGL(k_row_stats, dim3(rows), dim3(256), 0, s, a.x, a.E, a.eps, stats);
-  hipLaunchKernelGGL(k_lm_logits_rows, dim3(ceil_div(a.vocab, 4 * BL_C)), dim3(256), 0, s, a.head_w, a.x, rows, a.vocab, a.head_d, a.head_c,
-                     stats, logp);
-  hipLaunchKernelGGL(k_log_softmax_rows, dim3(rows), dim3(1024), 0, s, logp, a.vocab);
-  return hipGetLastError();
-}
-
 hipError_t launch_lm_beam_search(const DecoderArgs& a, const BeamArgs& b, hipStream_t s) {
   const int N = b.N, W = b.W, R = N * W, E = a.E, V = a.vocab;
   if (N < 1 || W < 1 || W > 8 || R > 128 || a.N != R || b.Pmax < 1 || b.Pmax > 128 || b.steps < 1 || b.steps > 64 ||
@@ -2780,20 +2732,13 @@ hipError_t launch_lm_beam_search(const DecoderArgs& a, const BeamArgs& b, hipStr
   const int tstride = a.max_steps;
   hipLaunchKernelGGL(k_beam_init, dim3(R), dim3(256), 0, s, b.plen, b.Pmax, W, tstride, b.steps, b.prow, b.pimg, b.tab, b.hist);
   // the prompts, once per image, on family A; image n's keys / values into cache row n W; x[n] = output of position P_n - 1
-  const int split = 1 << 30, Pmax = b.Pmax;
-  const int gmax = a.pre_rows / Pmax;
-  for (int n0 = 0; n0 < N; n0 += gmax) {
-    const int gN = N - n0 < gmax ? N - n0 : gmax;
-    hipLaunchKernelGGL(k_dec_prompt_x_all, dim3(gN, Pmax), dim3(256), 0, s, b.embeds + (size_t)n0 * Pmax * E, a.wpe, Pmax, E, a.pre_x);
-    PIO_TRY(dec_prefill_layers_masked<1>(a, n0, gN, Pmax, b.pimg + n0, split, s, W));
-    hipLaunchKernelGGL(k_dec_last_rows_ragged<1>, dim3(gN), dim3(256), 0, s, a.pre_x, Pmax, b.pimg + n0, split, E, a.x + (size_t)n0 * E);
-  }
-  PIO_TRY(beam_head(a, N, b.stats, b.logp, s));
+  PIO_TRY(dec_prompt_prefill<1>(a, N, b.embeds, b.Pmax, s, b.pimg, 1 << 30, W));
+  PIO_TRY(lm_head_rows(a, N, LOGITS_ROWS, true, b.stats, b.logp, s));
   hipLaunchKernelGGL(k_beam_step, dim3(N), dim3(1024), 0, s, b.logp, W, V, 0, b.eos0, b.eos1, b.prow, b.scores, b.lens, b.stopped, b.tok,
                      b.hist, b.steps, b.tab, tstride, a.wte, a.wpe, b.npos, E, a.x);
   for (int i = 1; i < b.steps; ++i) {
     PIO_TRY(dec_layers_step<true>(a, i - 1, s, b.prow, b.tab));     // row r at position P_n + i - 1
-    PIO_TRY(beam_head(a, R, b.stats, b.logp, s));
+    PIO_TRY(lm_head_rows(a, R, LOGITS_ROWS, true, b.stats, b.logp, s));
     hipLaunchKernelGGL(k_beam_step, dim3(N), dim3(1024), 0, s, b.logp, W, V, i, b.eos0, b.eos1, b.prow, b.scores, b.lens, b.stopped, b.tok,
                        b.hist, b.steps, b.tab, tstride, a.wte, a.wpe, b.npos, E, a.x);
   }
@@ -2823,15 +2768,6 @@ hipError_t launch_clipcap_mapping(const float* x, int N, int C, int H, int Nout,
   return hipGetLastError();
 }
 
-// x[n][:] = wte[ids[n][step]][:] + wpe[pos][:]
-__global__ __launch_bounds__(256) void k_sample_next_x(const int32_t* __restrict__ ids, int steps, int step, int pos, const float* __restrict__ wte,
-                                                       const float* __restrict__ wpe, int E, int V, float* x) {
-  const int n = blockIdx.x;
-  int t = ids[(size_t)n * steps + step];
-  t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-  for (int d = threadIdx.x; d < E; d += 256) x[(size_t)n * E + d] = wte[(size_t)t * E + d] + wpe[(size_t)pos * E + d];
-}
-
 // generate_batched (:198-311) with a KV cache: the prompt once (launch_decode_prompted's prefill), then per step the exact fp32 LM head on
 // every row (k_row_stats + k_lm_logits_rows: raw logits, the sampler needs no normalisation), k_nucleus_sample, and the drawn token's
 // embedding through the layers.  All a.steps steps run (no early exit: see DESIGN.md); rows that have stopped emit stop_id.
@@ -2841,31 +2777,17 @@ hipError_t launch_lm_sample(const DecoderArgs& a, const float* prompt, int P, fl
   if (P < 1 || a.steps < 1 || N < 1 || N > 128 || a.pos_base != P - 1 || P + a.steps - 1 > a.max_steps || a.max_steps > 256 || E != 768 ||
       (E / a.heads) % 32 != 0 || !uniforms || !active || !stats || !lens)
     return hipErrorInvalidValue;
-  if (a.pre_x != nullptr && P > 1 && P <= a.pre_rows) {
-    const int gmax = a.pre_rows / P;
-    for (int n0 = 0; n0 < N; n0 += gmax) {
-      const int gN = N - n0 < gmax ? N - n0 : gmax;
-      hipLaunchKernelGGL(k_dec_prompt_x_all, dim3(gN, P), dim3(256), 0, s, prompt + (size_t)n0 * P * E, a.wpe, P, E, a.pre_x);
-      PIO_TRY(dec_prefill_layers(a, n0, gN, P, s));
-      hipLaunchKernelGGL(k_dec_last_rows, dim3(gN), dim3(256), 0, s, a.pre_x, P, E, a.x + (size_t)n0 * E);
-    }
-  } else {
-    for (int pos = 0; pos < P; ++pos) {
-      hipLaunchKernelGGL(k_dec_prompt_x, dim3(N), dim3(256), 0, s, prompt, a.wpe, P, pos, E, a.x);
-      PIO_TRY(dec_layers_step(a, pos, s));
-    }
-  }
+  PIO_TRY(dec_prompt_prefill<0>(a, N, prompt, P, s));
   PIO_TRY(launch_sample_init(N, active, s));
   SampleArgs sa;
   sa.scores = a.logits; sa.N = N; sa.V = V; sa.ld = V; sa.temperature = temperature; sa.top_p = top_p; sa.u_stride = a.steps;
   sa.stop_id = stop_id; sa.active = active; sa.tok_stride = a.steps; sa.kept = nullptr;
   for (int step = 0; step < a.steps; ++step) {
-    hipLaunchKernelGGL(k_row_stats, dim3(N), dim3(256), 0, s, a.x, E, a.eps, stats);
-    hipLaunchKernelGGL(k_lm_logits_rows, dim3(ceil_div(V, 4 * BL_C)), dim3(256), 0, s, a.head_w, a.x, N, V, a.head_d, a.head_c, stats, a.logits);
+    PIO_TRY(lm_head_rows(a, N, LOGITS_ROWS, false, stats, a.logits, s));
     sa.uniforms = uniforms + step; sa.tokens = a.ids + step;
     PIO_TRY(launch_nucleus_sample(sa, s));
     if (step + 1 < a.steps) {
-      hipLaunchKernelGGL(k_sample_next_x, dim3(N), dim3(256), 0, s, a.ids, a.steps, step, P + step, a.wte, a.wpe, E, V, a.x);
+      hipLaunchKernelGGL(k_dec_token_x, dim3(N), dim3(256), 0, s, a.ids, a.steps, step, P + step, a.wte, a.wpe, E, V, a.x);
       PIO_TRY(dec_layers_step(a, P + step, s));
     }
   }

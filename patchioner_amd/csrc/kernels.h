@@ -375,6 +375,5 @@ struct PrepImage {
 hipError_t launch_preprocess(const uint8_t* pixels, const PrepImage* imgs, const int32_t* tables, uint8_t* tmp,
                              const float* lut, int B, int S, int max_tmp_elems, float* out, hipStream_t s);
 
-hipError_t decoder_init();   // one-time function attributes (call outside stream capture)
 
 }  // namespace pio

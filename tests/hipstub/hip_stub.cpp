@@ -86,6 +86,5 @@ hipError_t launch_viecap_mapping(const ViecapMapArgs&, hipStream_t) { return hip
 hipError_t launch_sgemm_tn(const float*, int, const float*, int, const float*, float, float*, int, int, int, int, int, int, hipStream_t) { return hipSuccess; }
 hipError_t launch_build_prompt(const float*, const int32_t*, const float*, int, int, int, int, int, int, float*, hipStream_t) { return hipSuccess; }
 hipError_t launch_preprocess(const uint8_t*, const PrepImage*, const int32_t*, uint8_t*, const float*, int, int, int, float*, hipStream_t) { return hipSuccess; }
-hipError_t decoder_init() { return hipSuccess; }
 hipError_t dec_split_weights(const float*, size_t, void*, float* unscale, hipStream_t) { *unscale = 1.f; return hipSuccess; }
 }  // namespace pio

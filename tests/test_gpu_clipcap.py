@@ -184,6 +184,29 @@ def test_device_philox_equals_the_host_copy(lib, model):
     clone.close()
 
 
+def test_sampling_prefill_batched_equals_position_by_position(tok, model, monkeypatch):
+    """pio_lm_sample takes its prompt through the decoder's one prompt prefill (decoder.hip: dec_prompt_prefill), as the prompted greedy
+    decode does: all N x P prompt rows as one batch by default, position by position on a handle created under PIO_DEC_PREFILL=0.  With
+    the same uniforms both handles must give the same ids and lens.  N = 3, P = 11, steps = 8: the prompts fit one group of the prefill
+    workspace (33 rows, one launch per GEMM).  This is no structural bit identity: the 33-row batch runs k_dec_gemm_b, which sums a GEMM
+    row in another order than the 3-row launches of k_dec_gemm, so the two caches differ at rounding level.  The ids are equal as long
+    as no such difference moves a draw across a CDF step, which holds for these seeded weights, inputs and uniforms; it is the same kind
+    of pin as the one test_gpu_viecap.py puts on the greedy ids of the two paths."""
+    N, P, steps = 3, 11, 8
+    stop = model.clipcap.stop_token_index
+    x = torch.randn(N, 768, generator=torch.Generator().manual_seed(3)).cuda()
+    prefix = model.engine.clipcap_mapping(x, normalize=True)
+    embeds = prefix.repeat(1, -(-P // prefix.shape[1]), 1)[:, :P].contiguous()
+    u = torch.rand(N, steps, generator=torch.Generator().manual_seed(4))
+    ids_b, lens_b = model.engine.lm_sample(embeds, steps, 1.0, 0.8, stop, uniforms=u)
+    monkeypatch.setenv("PIO_DEC_PREFILL", "0")
+    serial = _model(tok)
+    ids_s, lens_s = serial.engine.lm_sample(embeds, steps, 1.0, 0.8, stop, uniforms=u)
+    torch.cuda.synchronize()
+    assert ids_b.shape == (N, steps) and torch.equal(ids_b.cpu(), ids_s.cpu()) and torch.equal(lens_b.cpu(), lens_s.cpu())
+    serial.engine.close()
+
+
 @pytest.mark.parametrize("C", [512, 768, 1024])
 def test_mapper_against_float64(C):
     """The decode GEMMs' bar (tests/test_gpu_viecap_kernels.py): SAFETY sqrt(K_max) (levels) u relative to the largest output, K_max = 3840

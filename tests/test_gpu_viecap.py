@@ -127,7 +127,7 @@ def test_viecap_pieces_vs_reference_and_oracle(O, golden, case):
 
 
 def test_viecap_batched_prompt_prefill_gives_the_ids_of_the_position_by_position_path(case, monkeypatch):
-    """Round 5: the prompt of a ViECap decode goes through the layers as ONE batch of N x P rows (decoder.hip: dec_prefill_layers: the layer
+    """Round 5: the prompt of a ViECap decode goes through the layers as ONE batch of N x P rows (decoder.hip: dec_prompt_prefill: the layer
     GEMMs on 128 rows per launch, the keys / values of every position appended first) instead of P passes over N rows.  Same products,
     another order of the fp32 sums inside a GEMM row, so the cache differs at rounding level; the ids of both paths are held to each
     other here (32 prefixes with prompts of different lengths, padded as the reference pads them: pad id 0, no mask) and, in

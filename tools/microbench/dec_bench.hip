@@ -1,5 +1,6 @@
 // Stand-alone timing of the decoder kernels (diagnostic, never shipped):
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I patchioner_amd/csrc tools/microbench/dec_bench.hip -o dec_bench
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I patchioner_amd/csrc tools/microbench/dec_bench.hip patchioner_amd/csrc/sample.hip -o dec_bench
+// (sample.hip: decoder.hip's sampling loop calls its launchers.)
 // Each kernel is launched in a dependent chain of ITER launches on one stream (like the decode graph) and the
 // per-launch time is the elapsed time / ITER.
 #include "../../patchioner_amd/csrc/decoder.hip"
@@ -55,7 +56,6 @@ int main(int argc, char** argv) {
   CK(hipMemcpy(att, h.data(), (size_t)N * E * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(bias, h.data(), (size_t)V * 4, hipMemcpyHostToDevice));
   CK(hipMemcpy(cvec, h.data(), (size_t)V * 4, hipMemcpyHostToDevice));
   CK(hipMemset(kc, 0, (size_t)N * S * E * 4)); CK(hipMemset(vc, 0, (size_t)N * S * E * 4)); CK(hipMemset(qkv, 0, (size_t)N * 3 * E * 4));
-  CK(decoder_init());
   hipStream_t s = 0;
   int nblk = 0;
   printf("N=%d\n", N);
@@ -71,7 +71,7 @@ int main(int argc, char** argv) {
     auto step = [&] {
       for (int l = 0; l < 4; ++l) {
         dec_gemm<DE_STORE, 1>(wq[l], x, N, 3 * E, E, bias, qkv, nullptr, cvec, 1e-5f, nullptr, nullptr, s);
-        hipLaunchKernelGGL(k_dec_attention, dim3(N * heads), dim3(256), 0, s, qkv, kc, vc, E, heads, 15, S, att);
+        hipLaunchKernelGGL(k_dec_attention<false>, dim3(N * heads), dim3(256), 0, s, qkv, kc, vc, E, heads, 15, S, att, 1);
         dec_gemm<DE_RESID, 0>(wp[l], att, N, E, E, bias, x, nullptr, nullptr, 0.f, nullptr, nullptr, s);
         dec_gemm<DE_GELU, 1>(wf[l], x, N, 4 * E, E, bias, hid, nullptr, cvec, 1e-5f, nullptr, nullptr, s);
         dec_gemm<DE_RESID, 0>(wg[l], hid, N, E, 4 * E, bias, x, nullptr, nullptr, 0.f, ws, cnt, s);
@@ -122,8 +122,8 @@ int main(int argc, char** argv) {
            time_chain([&] { dec_gemm<DE_STORE, 1>(w2, x, N, 6 * E, E, bias, o2, nullptr, cvec, 1e-5f, nullptr, nullptr, s); dec_gemm<DE_RESID, 0>(w_proj, att, N, E, E, bias, x, nullptr, nullptr, 0.f, ws, cnt, s); }),
            time_chain([&] { dec_gemm<DE_STORE, 1>(w_qkv, x, N, 3 * E, E, bias, qkv, nullptr, cvec, 1e-5f, nullptr, nullptr, s); dec_gemm<DE_RESID, 0>(w_proj, att, N, E, E, bias, x, nullptr, nullptr, 0.f, ws, cnt, s); }));
   }
-  printf("attention pos=15   %7.2f us\n", time_chain([&] { hipLaunchKernelGGL(k_dec_attention, dim3(N * heads), dim3(256), 0, s, qkv, kc, vc, E, heads, 15, S, att); }));
-  printf("attention pos=29   %7.2f us\n", time_chain([&] { hipLaunchKernelGGL(k_dec_attention, dim3(N * heads), dim3(256), 0, s, qkv, kc, vc, E, heads, 29, S, att); }));
+  printf("attention pos=15   %7.2f us\n", time_chain([&] { hipLaunchKernelGGL(k_dec_attention<false>, dim3(N * heads), dim3(256), 0, s, qkv, kc, vc, E, heads, 15, S, att, 1); }));
+  printf("attention pos=29   %7.2f us\n", time_chain([&] { hipLaunchKernelGGL(k_dec_attention<false>, dim3(N * heads), dim3(256), 0, s, qkv, kc, vc, E, heads, 29, S, att, 1); }));
   printf("proj (resid)       %7.2f us\n", time_chain([&] { dec_gemm<DE_RESID, 0>(w_proj, att, N, E, E, bias, x, nullptr, nullptr, 0.f, ws, cnt, s); }));
   if (N > 16) {   // split-K sensitivity of the non-LN GEMMs (X traffic per workgroup / workgroup count)
     printf("proj KS2 CPW6      %7.2f us\n", time_chain([&] { dec_gemm_rg<6, 2, DE_RESID, 0>(w_proj, att, N, E, E, bias, x, nullptr, nullptr, 0.f, ws, cnt, s); }));
