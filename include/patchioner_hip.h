@@ -151,6 +151,19 @@ int pio_set_memory_bank_device(pio_handle h, const float* dev_bank, int64_t rows
 int pio_vit_forward(pio_handle h, const float* imgs_dev, int32_t B, float* tokens_dev, float* qkv_last_dev,
                     pio_stream stream);
 
+/* -- The same forward with a SPARSE last block, for callers that read only a few final tokens (trace regions: the region mean skips
+ *    every patch whose grid weight is 0).  The last block's keys and values need every token, so everything up to its qkv projection
+ *    runs on all rows; its query rows, attention output, proj, LayerNorm 2, fc1, fc2 and the final LayerNorm run on the listed rows only.
+ *    The unit is a quad: four consecutive rows of the padded token matrix [B * Tp] (Tp = T rounded up to 8) whose first row
+ *    b * Tp + t is a multiple of 4.  quads_host [nq] = first rows, strictly ascending; img_off_host [B + 1] = offsets of every image's
+ *    quads in that list, nq = img_off_host[B] (HOST memory, validated here and copied on `stream`: pinned memory must stay unchanged
+ *    until the copy has run).  pio_host_trace_quads builds both from trace points.
+ *    tokens_dev [4 * nq, D]: row 4 i + j = the final token of padded row quads[i] + j, bit-identical to pio_vit_forward's.
+ *    row_map_dev [B, n * n] int32: the compact row of every patch, -1 where it was not computed (pio_region_reduce_rows reads it).
+ *    fp16 / bf16 DINOv2 towers only; at most half of the launch's B * Tp rows may be listed (PIO_ERR_CAPACITY: call pio_vit_forward). */
+int pio_vit_forward_rows(pio_handle h, const float* imgs_dev, int32_t B, const int32_t* quads_host, const int32_t* img_off_host,
+                         float* tokens_dev, int32_t* row_map_dev, pio_stream stream);
+
 /* -- AlphaCLIP (vit_arch 2): one tower pass per region, the alpha mask as the fourth input channel
  *    (forward_alphaclip_with_regions, P/src/model.py:1060-1354).  All pointers DEVICE.
  *    imgs_dev           [B,3,crop,crop] fp32, the call's images
@@ -204,6 +217,12 @@ int pio_bbox_weights(pio_handle h, const int32_t* boxes_dev, int32_t B, int32_t 
  *    weights_dev [R,n*n]; img_index_dev [R] int32 (NULL = row r uses image r); out_dev [R,D]. */
 int pio_region_reduce(pio_handle h, const float* tokens_dev, int32_t B, const float* weights_dev,
                       const int32_t* img_index_dev, int32_t R, float scale, float* out_dev, pio_stream stream);
+
+/* The same reduction over the COMPACT tokens of pio_vit_forward_rows: patch p of image i is row row_map_dev[i * n*n + p] of
+ * tokens_dev (a patch without a row must carry weight 0).  row_map_dev points at the map of the first image the weights refer to.
+ * Same patches per wave, same order of the sum: the result is pio_region_reduce's on the dense tokens, bit for bit. */
+int pio_region_reduce_rows(pio_handle h, const float* tokens_dev, const int32_t* row_map_dev, const float* weights_dev,
+                           const int32_t* img_index_dev, int32_t R, float scale, float* out_dev, pio_stream stream);
 
 /* -- a8: fixed whole-image weight map (compute_region_means, P/src/model.py:45-94), variance > 0.
  *    map_dev [n*n]. variance >= 100 -> uniform. */
@@ -444,6 +463,12 @@ int pio_host_interpolate_pos_embed_plain(const float* pos, int32_t grid, int32_t
  * count * pio_host_pil_ksize(in_size, out_size) int32, bounds 2 * count (min, taps). */
 int pio_host_pil_ksize(int32_t in_size, int32_t out_size);
 int pio_host_pil_table(int32_t in_size, int32_t out_size, int32_t first, int32_t count, int32_t* kk, int32_t* bounds);
+/* Host-only: the quads a batch of traces needs (pio_vit_forward_rows).  xy [P, 2] float64, offsets [B + 1] CSR, as pio_trace_grids takes
+ * them but in HOST memory; n = grid side, G = 1 + registers, Tp = padded rows per image.  A quad is listed when one of its rows is a
+ * patch whose cell holds a point, by the arithmetic of pio_trace_grids (double: the [0, 1] test, x / (1.0 / n), the clamp to n - 1).
+ * quads [cap], img_off [B + 1].  Returns the number of quads (>= 0), or a negative error (bad sizes, more than cap). */
+int pio_host_trace_quads(const double* xy, const int32_t* offsets, int32_t B, int32_t n, int32_t G, int32_t Tp, int32_t* quads,
+                         int32_t cap, int32_t* img_off);
 /* The sampler's counter-based generator on the host (no device): Philox4x32-10, out[4] from counter ctr[4] and the 64-bit key
  * (key_lo, key_hi); and the uniform pio_lm_sample draws for (row, step) under `seed` -- the fp32 value k / 2^24, written to *u. */
 int pio_host_philox4x32(const uint32_t* ctr, uint32_t key_lo, uint32_t key_hi, uint32_t* out);

@@ -18,6 +18,7 @@
 #include "host_prep.h"
 #include "kernels.h"
 #include "resnet.h"
+#include "trace_rows.h"
 
 using namespace pio;
 
@@ -105,6 +106,13 @@ hipError_t launch_im2col_alpha(int, const float*, const int32_t*, const uint8_t*
 hipError_t launch_region_masks(const float*, const int32_t*, const double*, const int32_t*, int, int, float, uint8_t*, hipStream_t) __attribute__((weak));
 }  // namespace pio
 #define PIO_ALPHA_LINKED (&launch_im2col_alpha != nullptr && &launch_region_masks != nullptr)
+// the sparse last block's two launchers, likewise younger than the stub: pio_vit_forward_rows / pio_region_reduce_rows report
+// PIO_ERR_NOT_READY there
+namespace pio {
+hipError_t launch_gather_rows(const float*, const int32_t*, int, int, int, int, int, float*, int32_t*, hipStream_t) __attribute__((weak));
+hipError_t launch_region_reduce_rows(const float*, const int32_t*, int, int, const float*, const int32_t*, int, float, float*, hipStream_t) __attribute__((weak));
+}  // namespace pio
+#define PIO_ROWS_LINKED (&launch_gather_rows != nullptr && &launch_region_reduce_rows != nullptr)
 namespace pio {
 int rn_build(const pio_config&, const RnGet&, RnNet**) __attribute__((weak));
 void rn_destroy(RnNet*) __attribute__((weak));
@@ -113,6 +121,7 @@ int rn_forward(RnNet*, const float*, int, float*, hipStream_t) __attribute__((we
 #define PIO_RN_LINKED (&rn_build != nullptr && &rn_destroy != nullptr && &rn_forward != nullptr)
 #else
 #define PIO_ALPHA_LINKED true
+#define PIO_ROWS_LINKED true
 #define PIO_RN_LINKED true
 #endif
 
@@ -145,6 +154,8 @@ struct pio_context {
   float* x = nullptr; void* xn = nullptr; void* ao = nullptr; void* hbuf = nullptr; void* ape = nullptr;
   void *q = nullptr, *k = nullptr, *vT = nullptr;
   int32_t* seq_lens = nullptr;   // double-DINO boxes: token count of each sequence of the current chunk
+  // the sparse last block (pio_vit_forward_rows): compact residual rows [xs_rows][D] fp32, the launch's quad list and per-image offsets
+  float* xs = nullptr; int xs_rows = 0; int32_t* quads_dev = nullptr;
   // read-out workspaces
   float* head_logits = nullptr; float* head_sm = nullptr; int32_t* head_img = nullptr;
   // decoder weights
@@ -437,6 +448,11 @@ int finalize_vit(pio_context* c) {
   if ((rc = c->dmalloc_bytes(&c->q, qk, true))) return rc;
   if ((rc = c->dmalloc_bytes(&c->k, qk, true))) return rc;
   if ((rc = c->dmalloc_bytes(&c->vT, qk, true))) return rc;
+  if (c->cfg.vit_arch == 0) {
+    c->xs_rows = (int)(M / kSparseShareDen);
+    if ((rc = c->dmalloc(&c->xs, (size_t)c->xs_rows * D, true))) return rc;
+    if ((rc = c->dmalloc(&c->quads_dev, M / 4 + B + 1, true))) return rc;
+  }
   const int Hr = c->cfg.readout_heads;
   if ((rc = c->dmalloc(&c->head_logits, B * Hr * c->n2))) return rc;
   if ((rc = c->dmalloc(&c->head_sm, B * Hr * c->n2))) return rc;
@@ -1100,11 +1116,22 @@ static int run_vit_block_f32(pio_handle c, int l, int B, float* qkv_last, const 
 // row's softmax exactly 1 on itself): qkv + attention are replaced by the V-only projection, one GEMM over rows [2D, 3D) of in_proj
 // whose plain [M][D] output (EPI_BIAS) is the proj GEMM's A operand.  No q, k, score or softmax; next_self_only: what the fc2 GEMM's
 // spare workgroups warm for the next block.
+// rows (the sparse last block, pio_vit_forward_rows): LN1 and qkv run on every row -- the keys and values need every token -- and the
+// attention's queries, proj, LN2, fc1 and fc2 on the rows->nq listed quads only, compacted: the attention writes compact rows, the
+// residual rows are gathered into c->xs, and the GEMMs, which index nothing but [m][n], run in place on it with M = 4 nq.  Every
+// element is the dense block's, bit for bit: a GEMM output depends on its row's place only through `row mod 4` (resid_join_ktile),
+// which whole aligned quads keep; LayerNorm is per row; an attention query is one MFMA column.
+struct RowSel { const int32_t* quads; const int32_t* img_off; int nq, max_per_img; int32_t* row_map; };
+
 static int run_vit_block(pio_handle c, const VitLayerDev& L, int B, const GemmArgs& g, const VitAttnArgs& at,
                          float* qkv_last, hipStream_t s, const VitLayerDev* next = nullptr, bool self_only = false,
-                         bool next_self_only = false) {
+                         bool next_self_only = false, const RowSel* rows = nullptr) {
   const int D = c->D, M = B * c->Tp;
   const double Malg = (double)B * c->T;   // algorithmic rows: no pad tokens
+  // the rows everything behind the qkv GEMM runs on, and what the profile brackets attribute to it (the rows really computed)
+  const int Mt = rows ? 4 * rows->nq : M;
+  const double Mtalg = rows ? (double)Mt : Malg;
+  float* const xt = rows ? c->xs : c->x;
   // TIMING ablation, compiled only into diagnostic builds (-DPIO_ABLATIONS; tools/microbench/ln_ablation.sh): PIO_ABL_SKIP_LN=1 leaves
   // the two LayerNorm launches of every block out (wrong results) -- the upper bound of what ANY folding of LayerNorm into its
   // neighbours could save: +9.8 % captions/s through the pipeline, +3.9 % on a synchronous forward (profiles/r04_bench_sweep.log)
@@ -1129,38 +1156,45 @@ static int run_vit_block(pio_handle c, const VitLayerDev& L, int B, const GemmAr
     a.pf = L.projw; a.pf_bytes = D * D * 2;          // each GEMM's spare workgroups warm the next one's weights (GemmArgs::pf)
     PROF(c, PIO_PROF_VIT_GEMM, 2.0 * Malg * 3.0 * D * D, 0, s, launch_vit_gemm(c->op, EPI_QKV, a, s));
   }
+  if (rows) {
+    VitAttnArgs ar = at;
+    ar.quads = rows->quads; ar.img_off = rows->img_off; ar.max_rows = 4 * rows->max_per_img;
+    PROF(c, PIO_PROF_VIT_ATTN, 4.0 * Mtalg * c->T * D, 0, s, launch_vit_attention(c->op, ar, s));
+    HIP_OK(launch_gather_rows(c->x, rows->quads, rows->nq, c->T, c->Tp, c->G, D, c->xs, rows->row_map, s));
+  } else
   PROF(c, PIO_PROF_VIT_ATTN, 4.0 * B * (double)c->T * c->T * D, 0, s, launch_vit_attention(c->op, at, s));
   }
   {
     GemmArgs a = g;
-    a.A = c->ao; a.lda = D; a.W = L.projw; a.bias = L.projb_ls; a.M = M; a.N = D; a.K = D;
+    a.A = c->ao; a.lda = D; a.W = L.projw; a.bias = L.projb_ls; a.M = Mt; a.N = D; a.K = D; a.x = xt;
     a.pf = L.fc1w; a.pf_bytes = 4 * D * D * 2;
-    PROF(c, PIO_PROF_VIT_GEMM, 2.0 * Malg * D * D, 0, s, launch_vit_gemm(c->op, EPI_RESIDUAL, a, s));
+    PROF(c, PIO_PROF_VIT_GEMM, 2.0 * Mtalg * D * D, 0, s, launch_vit_gemm(c->op, EPI_RESIDUAL, a, s));
   }
   if (!skip_ln)
-  PROF(c, PIO_PROF_VIT_LN, 0, Malg * D * 6.0, s,
-       launch_layernorm(c->op, c->x, L.n2w, L.n2b, c->cfg.vit_ln_eps, M, D, c->xn, nullptr, c->T, c->Tp, s));
+  PROF(c, PIO_PROF_VIT_LN, 0, Mtalg * D * 6.0, s,
+       launch_layernorm(c->op, xt, L.n2w, L.n2b, c->cfg.vit_ln_eps, Mt, D, c->xn, nullptr, c->T, c->Tp, s));
   {
     GemmArgs a = g;
-    a.A = c->xn; a.lda = D; a.W = L.fc1w; a.bias = L.fc1b; a.out16 = c->hbuf; a.M = M; a.N = 4 * D; a.K = D;
+    a.A = c->xn; a.lda = D; a.W = L.fc1w; a.bias = L.fc1b; a.out16 = c->hbuf; a.M = Mt; a.N = 4 * D; a.K = D;
     a.act = c->cfg.vit_arch >= 1 ? 1 : 0;
     a.pf = L.fc2w; a.pf_bytes = 4 * D * D * 2;
-    PROF(c, PIO_PROF_VIT_GEMM, 2.0 * Malg * 4.0 * D * D, 0, s, launch_vit_gemm(c->op, EPI_GELU, a, s));
+    PROF(c, PIO_PROF_VIT_GEMM, 2.0 * Mtalg * 4.0 * D * D, 0, s, launch_vit_gemm(c->op, EPI_GELU, a, s));
   }
   {
     GemmArgs a = g;
-    a.A = c->hbuf; a.lda = 4 * D; a.W = L.fc2w; a.bias = L.fc2b_ls; a.M = M; a.N = D; a.K = 4 * D;
+    a.A = c->hbuf; a.lda = 4 * D; a.W = L.fc2w; a.bias = L.fc2b_ls; a.M = Mt; a.N = D; a.K = 4 * D; a.x = xt;
     if (next != nullptr && next_self_only) { a.pf = next->vw; a.pf_bytes = D * D * 2; }
     else if (next != nullptr) { a.pf = next->qkvw; a.pf_bytes = 3 * D * D * 2; }
-    PROF(c, PIO_PROF_VIT_GEMM, 2.0 * Malg * 4.0 * D * D, 0, s, launch_vit_gemm(c->op, EPI_RESIDUAL, a, s));
+    PROF(c, PIO_PROF_VIT_GEMM, 2.0 * Mtalg * 4.0 * D * D, 0, s, launch_vit_gemm(c->op, EPI_RESIDUAL, a, s));
   }
   return PIO_OK;
 }
 
 // The forward of B sequences.  AlphaCLIP (vit_arch 2): sequence r is image img_of_region[r] (null: r) with the alpha mask masks[r]
 // (u8 [B][S][S]; null: ones); the other families read image r and take no mask.
+// rows: the last block and the final norm on the listed quads only; `tokens` then receives the 4 rows->nq compact rows [.][D].
 static int vit_forward_impl(pio_handle c, const float* imgs, int32_t B, const int32_t* img_of_region, const uint8_t* masks, float* tokens,
-                            float* qkv_last, hipStream_t s) {
+                            float* qkv_last, hipStream_t s, const RowSel* rows = nullptr) {
   const int D = c->D, M = B * c->Tp;
   const bool alpha = c->cfg.vit_arch == 2;
   if (alpha && !PIO_ALPHA_LINKED) return fail(PIO_ERR_NOT_READY, "vit forward: the alpha-channel kernels are not linked");
@@ -1209,8 +1243,13 @@ static int vit_forward_impl(pio_handle c, const float* imgs, int32_t B, const in
   const int depth = c->cfg.depth, first_self = depth - c->cfg.vit_self_only_layers;     // blocks [first_self, depth) attend to themselves only
   for (int l = 0; l < depth; ++l) {
     const int rc = run_vit_block(c, c->vl[l], B, g, at, (l == depth - 1) ? qkv_last : nullptr, s, l + 1 < depth ? &c->vl[l + 1] : nullptr,
-                                 l >= first_self, l + 1 >= first_self);
+                                 l >= first_self, l + 1 >= first_self, l == depth - 1 ? rows : nullptr);
     if (rc != PIO_OK) return rc;
+  }
+  if (rows) {     // final norm of the compact rows, row i -> tokens[i] (one "image" of 4 nq rows: nothing is dropped or moved)
+    const int Mt = 4 * rows->nq;
+    HIP_OK(launch_layernorm(c->op, c->xs, c->norm_w, c->norm_b, c->cfg.vit_ln_eps, Mt, D, nullptr, tokens, Mt, Mt, s));
+    return PIO_OK;
   }
   if (c->vhead_w) {
     // CLIP: forward_features' final norm on every token, then the bias-free head on every token (model.py:788-790): exact fp32
@@ -1230,6 +1269,50 @@ int pio_vit_forward(pio_handle c, const float* imgs, int32_t B, float* tokens, f
   HIP_OK(hipSetDevice(c->cfg.device));
   if (c->cfg.vit_arch == 3) return rn_forward(c->rn, imgs, B, tokens, (hipStream_t)stream);
   return vit_forward_impl(c, imgs, B, nullptr, nullptr, tokens, qkv_last, (hipStream_t)stream);
+}
+
+int pio_vit_forward_rows(pio_handle c, const float* imgs, int32_t B, const int32_t* quads_host, const int32_t* img_off_host,
+                         float* tokens, int32_t* row_map, pio_stream stream) {
+  if (!c || !imgs || !tokens || !quads_host || !img_off_host || !row_map) return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward_rows: null argument");
+  if (!c->has_vit) return fail(PIO_ERR_NOT_READY, "pio_vit_forward_rows: backbone weights not loaded");
+  if (c->cfg.vit_arch != 0 || c->vit_f32 || !c->xs)
+    return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward_rows: the fp16 / bf16 DINOv2 ViT only (call pio_vit_forward)");
+  if (!PIO_ROWS_LINKED) return fail(PIO_ERR_NOT_READY, "pio_vit_forward_rows: the row-selection kernels are not linked");
+  if (B < 1 || B > c->cfg.max_batch) return fail(PIO_ERR_CAPACITY, "pio_vit_forward_rows: batch above max_batch");
+  RowSel r;
+  if (!quads_valid(quads_host, img_off_host, B, c->Tp, &r.max_per_img))
+    return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward_rows: quads must be ascending multiples of 4 inside their image, img_off ascending from 0");
+  r.nq = img_off_host[B];
+  if (r.nq < 1) return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward_rows: no row selected (nothing to compute)");
+  if (4 * r.nq > c->xs_rows || (int64_t)4 * r.nq * kSparseShareDen > (int64_t)B * c->Tp)
+    return fail(PIO_ERR_CAPACITY, "pio_vit_forward_rows: more than 1 / " + std::to_string(kSparseShareDen) + " of the launch's rows selected (call pio_vit_forward)");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  // the list and the offsets go up behind whatever the stream still runs on the previous launch's copy
+  int32_t* off_dev = c->quads_dev + (size_t)c->cfg.max_batch * c->Tp / 4;
+  HIP_OK(hipMemcpyAsync(c->quads_dev, quads_host, (size_t)r.nq * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(off_dev, img_off_host, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemsetAsync(row_map, 0xFF, (size_t)B * c->n2 * 4, s));
+  r.quads = c->quads_dev; r.img_off = off_dev; r.row_map = row_map;
+  return vit_forward_impl(c, imgs, B, nullptr, nullptr, tokens, nullptr, s, &r);
+}
+
+int pio_region_reduce_rows(pio_handle c, const float* tokens, const int32_t* row_map, const float* weights, const int32_t* img_index,
+                           int32_t R, float scale, float* out, pio_stream stream) {
+  if (!c || !tokens || !row_map || !weights || !out) return fail(PIO_ERR_INVALID_ARG, "pio_region_reduce_rows: null argument");
+  if (R < 1) return fail(PIO_ERR_INVALID_ARG, "pio_region_reduce_rows: empty input");
+  if (!PIO_ROWS_LINKED) return fail(PIO_ERR_NOT_READY, "pio_region_reduce_rows: the row-selection kernels are not linked");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  HIP_OK(launch_region_reduce_rows(tokens, row_map, c->Dout, c->n2, weights, img_index, R, scale, out, (hipStream_t)stream));
+  return PIO_OK;
+}
+
+int pio_host_trace_quads(const double* xy, const int32_t* offsets, int32_t B, int32_t n, int32_t G, int32_t Tp, int32_t* quads,
+                         int32_t cap, int32_t* img_off) {
+  if (!offsets || !quads || !img_off || B < 1 || cap < 0 || (offsets[B] > 0 && !xy)) return fail(PIO_ERR_INVALID_ARG, "pio_host_trace_quads: bad argument");
+  const int nq = trace_quads(xy, offsets, B, n, G, G + n * n, Tp, quads, cap, img_off);
+  if (nq < 0) return fail(PIO_ERR_INVALID_ARG, "pio_host_trace_quads: unusable sizes or offsets, or more quads than cap");
+  return nq;
 }
 
 int pio_vit_forward_regions(pio_handle c, const float* imgs, const int32_t* img_of_region, const uint8_t* masks, int32_t R, float* tokens,

@@ -93,6 +93,12 @@ struct VitAttnArgs {
   int B, H, T, Tp, Tk, D;
   float scale;     // head_dim^-0.5
   const int32_t* lens = nullptr;   // optional [B]: tokens of each sequence (keys >= lens[b] are masked); else T for all
+  // optional query-row indirection (the sparse last block, api.cpp run_vit_block_rows): image b's queries are the rows
+  // quads[i] + 0..3 (rows of the padded token matrix, b Tp + t) for i in [img_off[b], img_off[b + 1]), and query j of that list is
+  // written to row 4 img_off[b] + j of `out` (compact rows).  Keys and values stay all T tokens of the image, in the same tile order;
+  // a query is an MFMA column = one lane, so its bits do not depend on which tile or lane carries it.  max_rows = the longest
+  // per-image list (4 x quads), which sizes the grid.
+  const int32_t* quads = nullptr; const int32_t* img_off = nullptr; int max_rows = 0;
 };
 hipError_t launch_vit_attention(OperandType t, const VitAttnArgs& a, hipStream_t s);
 
@@ -140,6 +146,13 @@ hipError_t launch_box_seq_reduce(const float* x, const int32_t* lens, int Ns, in
                                  hipStream_t s);
 hipError_t launch_token_init(float* x, const float* cls, const float* pos0, const float* reg, int B, int R, int T,
                              int Tp, int D, hipStream_t s);
+// the sparse last block: xs[i] = x[quads[i >> 2] + (i & 3)] for the 4 nq compact rows (fp32 [.][D]), and row_map[b n2 + p] = i for
+// every compact row that is patch p of image b (row_map [B][n2] int32; the caller has filled it with -1)
+hipError_t launch_gather_rows(const float* x, const int32_t* quads, int nq, int T, int Tp, int G, int D, float* xs, int32_t* row_map,
+                              hipStream_t s);
+// The share of a launch's padded rows up to which the sparse last block runs (and its workspace is sized): 1 / kSparseShareDen.  Until
+// the cut-over is measured it is one half; Engine.SPARSE_SHARE_DEN mirrors it.
+static constexpr int kSparseShareDen = 2;
 
 // ---- resnet.hip: RegionCLIP's CLIP ModifiedResNet tower (vit_arch 3); type 0 fp16, 1 bf16, 2 exact fp32 (the parity mode)
 struct ConvArgs {
@@ -176,6 +189,10 @@ hipError_t launch_bbox_weights(const int32_t* boxes, int B, int NB, int n, int m
                                float* single, hipStream_t s);
 hipError_t launch_region_reduce(const float* tokens, int T, int G, int D, int n2, const float* weights,
                                 const int32_t* img_index, int R, float scale, float* out, hipStream_t s);
+// The same over COMPACT tokens [.][D] (the sparse last block): patch p of image i is row row_map[i n2 + p] (row_map [images][n2] int32;
+// < 0: not computed -- such a patch must carry weight 0 and is skipped).  Same patches per wave, same order, same four-wave sum.
+hipError_t launch_region_reduce_rows(const float* tokens, const int32_t* row_map, int D, int n2, const float* weights,
+                                     const int32_t* img_index, int R, float scale, float* out, hipStream_t s);
 hipError_t launch_ctx_clean(const float* dirty, const float* ctx, int R, int D, int rows_per_ctx, int mode, float alpha,
                             int normalize_inputs, float* out, hipStream_t s);
 hipError_t launch_gaussian_map(int n, float variance, float* map, hipStream_t s);

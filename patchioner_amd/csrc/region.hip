@@ -78,24 +78,33 @@ __global__ __launch_bounds__(256) void k_softmax_rows(const float* __restrict__ 
 // small), NaN weights propagate like the reference's NaN means.
 __global__ __launch_bounds__(256) void k_region_reduce(const float* __restrict__ tokens, int T, int G, int D, int n2,
                                                        const float* __restrict__ w, const int32_t* img_index,
-                                                       float scale, float* out) {
+                                                       float scale, float* out, const int32_t* __restrict__ row_map) {
   // grid (R, ceil(D/256)): lane = one float4 column of a 256-channel slab; the 4 waves split the patches
   // (p = wave, wave+4, ...) with the weight row staged in LDS, then meet in LDS.
   __shared__ float s_w[1536];
   __shared__ __attribute__((aligned(16))) float s_acc[4][256];
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int img = img_index ? img_index[r] : r;
-  for (int p = tid; p < n2; p += 256) s_w[p] = w[(size_t)r * n2 + p];
+  // row_map: compact tokens (the sparse last block), patch p of the image is row rm[p], staged beside the weights; else the dense
+  // [B][T][D] layout
+  __shared__ int32_t s_rm[1536];
+  const int32_t* rm = row_map ? row_map + (size_t)img * n2 : nullptr;
+  for (int p = tid; p < n2; p += 256) {
+    s_w[p] = w[(size_t)r * n2 + p];
+    if (rm) s_rm[p] = rm[p];
+  }
   __syncthreads();
   const int c = blockIdx.y * 64 + lane;            // float4 column
   const bool live = c * 4 < D;
-  const float4* base = (const float4*)(tokens + ((size_t)img * T + G) * D) + (live ? c : 0);
+  const float4* base = (rm ? (const float4*)tokens : (const float4*)(tokens + ((size_t)img * T + G) * D)) + (live ? c : 0);
   const int stride = D >> 2;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int p = wid; p < n2; p += 4) {
     const float wv = s_w[p];
     if (wv == 0.f) continue;                        // wave-uniform: regions are small
-    const float4 t = base[(size_t)p * stride];
+    int row = p;
+    if (rm) { row = s_rm[p]; if (row < 0) continue; } // a weighted patch always has a row (trace_rows.h); never index with -1
+    const float4 t = base[(size_t)row * stride];
     acc.x += wv * t.x; acc.y += wv * t.y; acc.z += wv * t.z; acc.w += wv * t.w;
   }
   *(float4*)&s_acc[wid][4 * lane] = acc;
@@ -282,7 +291,16 @@ hipError_t launch_bbox_weights(const int32_t* boxes, int B, int NB, int n, int m
 hipError_t launch_region_reduce(const float* tokens, int T, int G, int D, int n2, const float* weights,
                                 const int32_t* img_index, int R, float scale, float* out, hipStream_t s) {
   if (D % 4 != 0 || D > 1024 || R <= 0 || n2 > 1536) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_region_reduce, dim3(R, ceil_div(D, 256)), dim3(256), 0, s, tokens, T, G, D, n2, weights, img_index, scale, out);
+  hipLaunchKernelGGL(k_region_reduce, dim3(R, ceil_div(D, 256)), dim3(256), 0, s, tokens, T, G, D, n2, weights, img_index, scale, out,
+                     (const int32_t*)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_region_reduce_rows(const float* tokens, const int32_t* row_map, int D, int n2, const float* weights,
+                                     const int32_t* img_index, int R, float scale, float* out, hipStream_t s) {
+  if (D % 4 != 0 || D > 1024 || R <= 0 || n2 > 1536 || row_map == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_region_reduce, dim3(R, ceil_div(D, 256)), dim3(256), 0, s, tokens, 0, 0, D, n2, weights, img_index, scale, out,
+                     row_map);
   return hipGetLastError();
 }
 

@@ -97,11 +97,19 @@ __global__ __launch_bounds__(256, PIO_ATTN_OCC) void k_vit_attention(const VitAt
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int h = lane >> 5, r31 = lane & 31;
   int qblk, bh;                              // bh = b*H + head
-  if (!attn_block((a.Tp + 127) / 128, a.B * a.H, qblk, bh)) return;
+  if (!attn_block(((a.quads ? a.max_rows : a.Tp) + 127) / 128, a.B * a.H, qblk, bh)) return;
   const int b = bh / a.H, head = bh - b * a.H;
   const int nkeys = a.lens ? a.lens[b] : a.T;     // keys of this sequence (block-uniform)
+  // query rows of this image: all Tp padded rows, or the listed ones (VitAttnArgs::quads), written compactly from row orow0 on
+  int nrows = a.Tp, orow0 = b * a.Tp, quad0 = 0;
+  if (a.quads) {
+    quad0 = a.img_off[b];
+    nrows = 4 * (a.img_off[b + 1] - quad0);
+    orow0 = 4 * quad0;
+    if (qblk * 128 >= nrows) return;         // block-uniform, before any barrier: nothing of this image in this query block
+  }
   const int q0 = qblk * 128 + wid * 32;
-  const bool active = q0 < a.Tp;             // wave-uniform
+  const bool active = q0 < nrows;            // wave-uniform
   const T* qb = (const T*)a.q + (size_t)bh * a.Tk * 64;
   const T* kb = (const T*)a.k + (size_t)bh * a.Tk * 64;
   const T* vb = (const T*)a.vT + (size_t)bh * 64 * a.Tk;
@@ -110,6 +118,10 @@ __global__ __launch_bounds__(256, PIO_ATTN_OCC) void k_vit_attention(const VitAt
   frag_t qf[4];
   {
     int qr = q0 + r31;
+    if (a.quads) {                           // listed query j = row quads[j / 4] + j % 4 of the padded matrix; past the list: a copy of its last
+      const int j = qr < nrows ? qr : nrows - 1;
+      qr = a.quads[quad0 + (j >> 2)] + (j & 3) - b * a.Tp;
+    }
     qr = qr < a.Tk ? qr : a.Tk - 1;
 #pragma unroll
     for (int s = 0; s < 4; ++s) qf[s] = *(const frag_t*)(qb + (size_t)qr * 64 + 16 * s + 8 * h);
@@ -283,9 +295,9 @@ __global__ __launch_bounds__(256, PIO_ATTN_OCC) void k_vit_attention(const VitAt
 
   if (active) {
     const int q = q0 + r31;
-    if (q < a.Tp) {
+    if (q < nrows) {
       const float inv = 1.0f / l_run;
-      T* orow = (T*)a.out + (size_t)(b * a.Tp + q) * a.D + head * 64;
+      T* orow = (T*)a.out + (size_t)(orow0 + q) * a.D + head * 64;
 #pragma unroll
       for (int d = 0; d < 2; ++d)
 #pragma unroll
@@ -301,7 +313,8 @@ __global__ __launch_bounds__(256, PIO_ATTN_OCC) void k_vit_attention(const VitAt
 
 hipError_t launch_vit_attention(OperandType t, const VitAttnArgs& a, hipStream_t s) {
   if (a.D != a.H * 64 || a.Tk % KV_TILE != 0 || a.Tk < a.Tp || a.Tp < a.T) return hipErrorInvalidValue;
-  dim3 grid(ceil_div(a.Tp, 128) * ceil_div(a.B * a.H, 8) * 8);
+  if (a.quads != nullptr && (a.img_off == nullptr || a.lens != nullptr || a.max_rows < 4 || a.max_rows > a.Tp)) return hipErrorInvalidValue;
+  dim3 grid(ceil_div(a.quads ? a.max_rows : a.Tp, 128) * ceil_div(a.B * a.H, 8) * 8);
   if (t == OP_F16) hipLaunchKernelGGL((k_vit_attention<f16>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((k_vit_attention<bf16>), grid, dim3(256), 0, s, a);
   return hipGetLastError();

@@ -126,6 +126,27 @@ hipError_t launch_token_init(float* x, const float* cls, const float* pos0, cons
   return hipGetLastError();
 }
 
+// The sparse last block's gather: one workgroup per compact row (kernels.h, launch_gather_rows).
+__global__ __launch_bounds__(256) void k_gather_rows(const float* __restrict__ x, const int32_t* __restrict__ quads, int Tt, int Tp,
+                                                     int G, int D, float* __restrict__ xs, int32_t* __restrict__ row_map) {
+  const int i = blockIdx.x;
+  const int src = quads[i >> 2] + (i & 3);
+  const float4* s4 = (const float4*)(x + (size_t)src * D);
+  float4* d4 = (float4*)(xs + (size_t)i * D);
+  for (int c = threadIdx.x; c < D / 4; c += 256) d4[c] = s4[c];
+  if (threadIdx.x == 0 && row_map != nullptr) {
+    const int b = src / Tp, t = src - b * Tp;
+    if (t >= G && t < Tt) row_map[(size_t)b * (Tt - G) + (t - G)] = i;
+  }
+}
+
+hipError_t launch_gather_rows(const float* x, const int32_t* quads, int nq, int T, int Tp, int G, int D, float* xs, int32_t* row_map,
+                              hipStream_t s) {
+  if (nq < 1 || D % 4 != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_gather_rows, dim3(4 * nq), dim3(256), 0, s, x, quads, T, Tp, G, D, xs, row_map);
+  return hipGetLastError();
+}
+
 
 // ---- double-DINO boxes: gather the block input of every (image, box) sequence ------------------------------
 __global__ __launch_bounds__(256) void k_box_sequences(const float* __restrict__ tokens, const int32_t* __restrict__ slices,

@@ -22,6 +22,10 @@ def _stream() -> int:
 
 
 class Engine:
+    # The sparse last block is taken while the selected rows stay below 1 / SPARSE_SHARE_DEN of the launch's padded rows: the library's
+    # kSparseShareDen (kernels.h), which also sizes its workspace.  One half until the cut-over is measured.
+    SPARSE_SHARE_DEN = 2
+
     def __init__(self, *, embed_dim: int, depth: int, num_heads: int, num_registers: int, crop_dim: int,
                  patch_size: int = 14, pretrain_grid: int = 37, prefix_size: int = 768, dec_layers: int = 4,
                  dec_heads: int = 4, dec_embd: int = 768, dec_vocab: int = 50257, dec_positions: int = 1024,
@@ -60,6 +64,9 @@ class Engine:
         self.bank_dim = 0
         self._finalized = False
         self._stage_ring = [dict(host=None, dev=None, event=None) for _ in range(8)]
+        self.Tp = (self.T + 7) // 8 * 8          # padded rows per image of the token matrix
+        # the sparse last block (pio_vit_forward_rows): fp16 / bf16 DINOv2 towers
+        self.sparse_ok = vit_arch == "dinov2" and vit_dtype in ("fp16", "bf16") and not vit_self_only_layers
         self._stage_next = 0
 
     def close(self):
@@ -214,21 +221,28 @@ class Engine:
         return self_attn, maps, avg, dis
 
     # ------------------------------------------------------------------ a6 traces
-    def trace_grids(self, traces: Sequence[Sequence[dict]]) -> torch.Tensor:
+    def trace_grids(self, traces: Sequence[Sequence[dict]], select_rows: bool = False):
         """map_traces_to_grid for a batch: points packed CSR-style into ONE pinned staging buffer (x, y as
         float64 followed by the int32 offsets) and sent with one asynchronous copy; the counting runs on
         the device.  A ring of 8 staging slots (each guarded by an event) lets the host run several batches
-        ahead of the GPU without overwriting a buffer whose copy has not executed yet."""
+        ahead of the GPU without overwriting a buffer whose copy has not executed yet.
+
+        ``select_rows``: returns (grids, sel).  The rows of the token matrix whose patches received a point are selected on the
+        host from the staged points (pio_host_trace_quads, the device's cell arithmetic) and kept in the same staging slot; ``sel``
+        is what vit_forward_rows takes, or None when the sparse last block does not apply (nothing selected, more than
+        1 / SPARSE_SHARE_DEN of the rows, more images than one launch holds)."""
         B = len(traces)
         xy = np.array([(p["x"], p["y"]) for tr in traces for p in tr], dtype=np.float64).reshape(-1, 2)
         npts = xy.shape[0]
         nbytes = npts * 16 + (B + 1) * 4
+        qcap = B * self.Tp // 4 if select_rows else 0
+        sel_bytes = (B + 1 + qcap) * 4           # img_off [B + 1] | quads [<= B Tp / 4], behind the uploaded part
         slot = self._stage_ring[self._stage_next % len(self._stage_ring)]
         self._stage_next += 1
         if slot["event"] is not None:
             slot["event"].synchronize()
-        if slot["host"] is None or slot["host"].numel() < nbytes:
-            cap = max(1 << 16, 2 * nbytes)
+        if slot["host"] is None or slot["host"].numel() < nbytes + sel_bytes:
+            cap = max(1 << 16, 2 * (nbytes + sel_bytes))
             slot["host"] = torch.empty(cap, dtype=torch.uint8).pin_memory()
             slot["dev"] = torch.empty(cap, dtype=torch.uint8, device=self.device)
         host = slot["host"].numpy()
@@ -243,7 +257,41 @@ class Engine:
         if slot["event"] is None:
             slot["event"] = torch.cuda.Event()
         slot["event"].record(torch.cuda.current_stream())
-        return grids
+        if not select_rows:
+            return grids
+        sel = None
+        if self.sparse_ok and B <= self.max_batch:
+            hbase = slot["host"].data_ptr()
+            nq = self.lib.pio_host_trace_quads(hbase if npts else None, hbase + npts * 16, B, self.n, self.G, self.Tp,
+                                               hbase + nbytes + (B + 1) * 4, qcap, hbase + nbytes)
+            if nq < 0:
+                check(nq)
+            if 0 < nq and 4 * nq * self.SPARSE_SHARE_DEN < B * self.Tp:
+                sel = dict(slot=slot, img_off=hbase + nbytes, quads=hbase + nbytes + (B + 1) * 4, nq=int(nq), B=B)
+        return grids, sel
+
+    def vit_forward_rows(self, imgs: torch.Tensor, sel: dict) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The backbone with the sparse last block (pio_vit_forward_rows) for the rows ``sel`` lists (trace_grids(select_rows=True)
+        of the same images, in order) -> (compact final tokens [4 nq, D], row_map int32 [B, n2] for region_reduce_rows)."""
+        imgs = self._dev(imgs)
+        B, crop = imgs.shape[0], self.cfg.crop_dim
+        if tuple(imgs.shape[1:]) != (3, crop, crop) or B != sel["B"]:
+            raise ValueError("images must be [%d,3,%d,%d], got %s" % (sel["B"], crop, crop, tuple(imgs.shape)))
+        tokens = torch.empty(4 * sel["nq"], self.D, device=self.device, dtype=torch.float32)
+        row_map = torch.empty(B, self.n2, device=self.device, dtype=torch.int32)
+        check(self.lib.pio_vit_forward_rows(self.h, ptr(imgs), B, sel["quads"], sel["img_off"], ptr(tokens), ptr(row_map), _stream()))
+        sel["slot"]["event"].record(torch.cuda.current_stream())      # the list is copied from the staging slot on this stream
+        return tokens, row_map
+
+    def region_reduce_rows(self, tokens: torch.Tensor, row_map: torch.Tensor, weights: torch.Tensor, scale: float) -> torch.Tensor:
+        """region_reduce over the compact tokens of vit_forward_rows: row r of ``weights`` weighs the patches of the image whose map
+        is row r of ``row_map`` (a slice of the launch's map)."""
+        weights = self._dev(weights.reshape(-1, self.n2))
+        R = weights.shape[0]
+        assert row_map.shape[0] == R and row_map.is_contiguous()
+        out = torch.empty(R, self.D, device=self.device, dtype=torch.float32)
+        check(self.lib.pio_region_reduce_rows(self.h, ptr(tokens), ptr(row_map), ptr(weights), None, R, float(scale), ptr(out), _stream()))
+        return out
 
     # ------------------------------------------------------------------ a7 boxes
     def bbox_weights(self, boxes_i32: torch.Tensor, mode: int, variance: float = 0.5,

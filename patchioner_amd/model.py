@@ -278,6 +278,8 @@ class Patchioner(nn.Module):
         self._device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
 
         self.normalize = normalize
+        # traces-only calls run the backbone's last block on the rows the traces read (forward, TraceCaptionPipeline); False: always dense
+        self.sparse_last_block = True
         self.resize_dim = resize_dim
         self.crop_dim = crop_dim
         self.model_name = dino_model
@@ -614,6 +616,17 @@ class Patchioner(nn.Module):
         eng = self.engine
         outs = {}
         bs = imgs.shape[0]
+        # Traces and nothing else that reads the final tokens: only the patches the traces touch are needed, and the last block runs
+        # on those rows alone (Engine.vit_forward_rows; the same bits as the dense forward, which stays the path of every other call).
+        if (self.sparse_last_block and traces is not None and eng.sparse_ok and bs <= eng.max_batch
+                and not (get_cls_capt or get_avg_self_attn_capt or get_attn_heads_capt or get_patch_capts or get_register_capts
+                         or get_avg_patch_capt or bboxes is not None or use_attention_tracing or cleaning_type is not None)):
+            grids, sel = eng.trace_grids(traces, select_rows=True)
+            if sel is not None:
+                tokens_c, row_map = eng.vit_forward_rows(imgs, sel)
+                trace_embeds = eng.region_reduce_rows(tokens_c, row_map, grids.view(bs, -1), 1.0 / self.num_patch_tokens)
+                outs['trace_capts'] = self.caption_tokens(trace_embeds)
+                return outs
         # has_attention (model.py:864-865): only DINO backbones install the qkv hook.  Without it the reference never defines
         # self_attn / avg_self_attn_token / disentangled_self_attn and every option that reads them fails with
         # UnboundLocalError; clean_from == "avg_self_attn" falls back to the cls token (:886-890).

@@ -102,7 +102,7 @@ class TraceCaptionPipeline:
     def __init__(self, model, group_batches: int = 4, use_attention_tracing: bool = False, steps: int = 30,
                  stage_replicas: Sequence = (), stage_cus: Optional[int] = None, decode_cus: Optional[int] = None,
                  vit_batches: int = 1, decode_replicas: Sequence = (), decode_clones: int = 0, eager_first: bool = False,
-                 beam_search: bool = False):
+                 beam_search: bool = False, sparse_last_block: Optional[bool] = None):
         """``stage_replicas``: further Patchioner instances holding the SAME weights (each has its own ViT
         workspace); stage 1 of consecutive batches then alternates over the replicas, each on its own stream,
         so that one batch's GEMM tails, epilogues and launch gaps are filled by the other's kernels."""
@@ -152,6 +152,9 @@ class TraceCaptionPipeline:
         # batches of a ViT launch are projected in one call: 80 queries = 48 + 32 (0.92 ms) instead of 32 + 32 + 16 (1.25 ms).
         self.project_batches = max(1, int(os.environ.get("PIO_PROJECT_BATCHES", "0")) or self.vit_batches)
         self.use_attention_tracing = use_attention_tracing
+        # A ViT launch whose batches are all plain traces reads only the patches the traces touch: its last block then runs on those
+        # rows alone (Engine.vit_forward_rows; same bits).  None: the model's setting; False: the dense forward always.
+        self.sparse_last_block = bool(getattr(model, "sparse_last_block", True) if sparse_last_block is None else sparse_last_block)
         self.steps = steps
         # Stage 1 may be confined to the first `stage_cus` compute units so that the decode's small dependent
         # kernels find idle CUs instead of queueing behind resident GEMM workgroups (None / 0: no restriction).
@@ -291,11 +294,20 @@ class TraceCaptionPipeline:
             imgs = held[0][0] if len(held) == 1 else torch.cat([h[0] for h in held], dim=0)
             want_qkv = any((self.use_attention_tracing and h[1] is not None and not isinstance(h[1], BoxRegions)) or
                            (isinstance(h[1], BoxRegions) and h[1].use_attn_map) for h in held)
-            tokens_all, qkv_all = eng.vit_forward(imgs, want_qkv=want_qkv)
+            # the sparse last block: every batch of the launch is plain traces (no attention tracing, no box, no CLS caption) -> the
+            # launch's grids and row list first, then the forward on those rows; the region mean stays per batch
+            grids_all = sel = tokens_c = row_map = None
+            if (self.sparse_last_block and eng.sparse_ok and not self.use_attention_tracing and imgs.shape[0] <= eng.max_batch
+                    and all(h[1] is not None and not isinstance(h[1], BoxRegions) for h in held)):
+                grids_all, sel = eng.trace_grids([tr for h in held for tr in h[1]], select_rows=True)
+            if sel is not None:
+                tokens_c, row_map = eng.vit_forward_rows(imgs, sel)
+            else:
+                tokens_all, qkv_all = eng.vit_forward(imgs, want_qkv=want_qkv)
             s = 0
             for im, traces, g in held:
                 n = im.shape[0]
-                tokens = tokens_all[s:s + n]
+                tokens = tokens_all[s:s + n] if sel is None else None
                 if isinstance(traces, BoxRegions):
                     # extract_bboxes_feats on this batch's tokens (model._bbox_feats: boxes //= patch_size in place, host draw of
                     # the var == 0 centre cells, weights and the weighted means on the device)
@@ -311,11 +323,14 @@ class TraceCaptionPipeline:
                 if traces is None:
                     emb = tokens[:, 0].contiguous()
                 else:
-                    grids = eng.trace_grids(traces).view(n, -1)
+                    grids = (eng.trace_grids(traces) if grids_all is None else grids_all[s:s + n]).view(n, -1)
                     if self.use_attention_tracing:
                         self_attn, _, _, _ = eng.cls_attention(qkv_all[s:s + n], tokens)
                         grids = self_attn * grids
-                    emb = eng.region_reduce(tokens, grids, None, 1.0 / m.num_patch_tokens)
+                    if sel is not None:
+                        emb = eng.region_reduce_rows(tokens_c, row_map[s:s + n], grids, 1.0 / m.num_patch_tokens)
+                    else:
+                        emb = eng.region_reduce(tokens, grids, None, 1.0 / m.num_patch_tokens)
                 s += n
                 if self.viecap is not None:
                     # caption_tokens hands the raw region features to the ViECap head (no bank projection): mapping network, entity
