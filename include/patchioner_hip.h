@@ -153,14 +153,16 @@ int pio_vit_forward(pio_handle h, const float* imgs_dev, int32_t B, float* token
 
 /* -- The same forward with a SPARSE last block, for callers that read only a few final tokens (trace regions: the region mean skips
  *    every patch whose grid weight is 0).  The last block's keys and values need every token, so everything up to its qkv projection
- *    runs on all rows; its query rows, attention output, proj, LayerNorm 2, fc1, fc2 and the final LayerNorm run on the listed rows only.
+ *    runs on all rows; its query rows, attention output, proj, LayerNorm 2, fc1, fc2 and the final LayerNorm -- on the CLIP ViT also the
+ *    head behind it -- run on the listed rows only.
  *    The unit is a quad: four consecutive rows of the padded token matrix [B * Tp] (Tp = T rounded up to 8) whose first row
  *    b * Tp + t is a multiple of 4.  quads_host [nq] = first rows, strictly ascending; img_off_host [B + 1] = offsets of every image's
  *    quads in that list, nq = img_off_host[B] (HOST memory, validated here and copied on `stream`: pinned memory must stay unchanged
  *    until the copy has run).  pio_host_trace_quads builds both from trace points.
- *    tokens_dev [4 * nq, D]: row 4 i + j = the final token of padded row quads[i] + j, bit-identical to pio_vit_forward's.
+ *    tokens_dev [4 * nq, Dout]: row 4 i + j = the final token of padded row quads[i] + j, bit-identical to pio_vit_forward's (Dout =
+ *    vit_out_dim behind the CLIP head, else D).
  *    row_map_dev [B, n * n] int32: the compact row of every patch, -1 where it was not computed (pio_region_reduce_rows reads it).
- *    fp16 / bf16 DINOv2 towers only; at most half of the launch's B * Tp rows may be listed (PIO_ERR_CAPACITY: call pio_vit_forward). */
+ *    fp16 / bf16 DINOv2 towers and CLIP ViTs (vit_arch 1) without self-only blocks only; at most half of the launch's B * Tp rows may be listed (PIO_ERR_CAPACITY: call pio_vit_forward). */
 int pio_vit_forward_rows(pio_handle h, const float* imgs_dev, int32_t B, const int32_t* quads_host, const int32_t* img_off_host,
                          float* tokens_dev, int32_t* row_map_dev, pio_stream stream);
 

@@ -31,14 +31,17 @@ PROJECTION_TYPES = {            # ProjectionType values (im2txtprojection.py:18-
 
 
 def filename_components(projection_type="coco_captions", use_talk2dino=True, linear_talk2dino=False, talk2dino_attn_type="qkv",
-                        memory_bank_name=None, use_open_clip=False) -> Tuple[str, str, str, str]:
+                        memory_bank_name=None, use_open_clip=False, denseclip_config=None) -> Tuple[str, str, str, str]:
     """(prefix, dataset_name, talk2dino_attn_type_str, postfix) -- ``_build_filename_components`` (:80-170) for the
-    configurations this package serves (Talk2DINO / plain CLIP / OpenCLIP banks; the RegionCLIP / INViTE / DenseClip
-    prefixes belong to backbones outside the path)."""
+    configurations this package serves (Talk2DINO / plain CLIP / OpenCLIP / DenseCLIP banks; the RegionCLIP / INViTE
+    prefixes belong to banks of text towers outside the path).  ``denseclip_config``: the config NAME (or a .yaml path), as the
+    reference takes it (:115-117, 168-173): prefix ``denseclip-`` without Talk2DINO, postfix ``-denseclip-<config base name>``."""
     if use_talk2dino:
         prefix, postfix = "", ("-B16" if use_talk2dino is True else use_talk2dino)
         if linear_talk2dino:
             postfix += "-linear"
+    elif denseclip_config is not None:
+        prefix, postfix = "denseclip-", ""
     else:
         prefix, postfix = "clip-", ""
     attn = "" if talk2dino_attn_type == "qkv" else "_%s" % talk2dino_attn_type
@@ -57,6 +60,13 @@ def filename_components(projection_type="coco_captions", use_talk2dino=True, lin
         dataset_name = "coco_captions" if use_talk2dino else "coco"
     if use_open_clip:
         postfix += "-open_clip"
+    elif denseclip_config is not None:
+        if not isinstance(denseclip_config, (str, os.PathLike)):
+            raise TypeError("denseclip_config: the bank's file name carries the config NAME (a str), got %s" % type(denseclip_config).__name__)
+        config_name = os.path.basename(os.fspath(denseclip_config)).replace(".yaml", "").replace(".yml", "")
+        postfix += "-denseclip"
+        if config_name:
+            postfix += "-" + config_name
     return prefix, dataset_name, attn, postfix
 
 

@@ -448,7 +448,8 @@ int finalize_vit(pio_context* c) {
   if ((rc = c->dmalloc_bytes(&c->q, qk, true))) return rc;
   if ((rc = c->dmalloc_bytes(&c->k, qk, true))) return rc;
   if ((rc = c->dmalloc_bytes(&c->vT, qk, true))) return rc;
-  if (c->cfg.vit_arch == 0) {
+  // DINOv2, and the plain CLIP ViT (no alpha channel, no self-only block: a self-only last block is row-local and wants another cut)
+  if (!c->vit_f32 && (c->cfg.vit_arch == 0 || (c->cfg.vit_arch == 1 && c->cfg.vit_self_only_layers == 0))) {
     c->xs_rows = (int)(M / kSparseShareDen);
     if ((rc = c->dmalloc(&c->xs, (size_t)c->xs_rows * D, true))) return rc;
     if ((rc = c->dmalloc(&c->quads_dev, M / 4 + B + 1, true))) return rc;
@@ -1192,7 +1193,8 @@ static int run_vit_block(pio_handle c, const VitLayerDev& L, int B, const GemmAr
 
 // The forward of B sequences.  AlphaCLIP (vit_arch 2): sequence r is image img_of_region[r] (null: r) with the alpha mask masks[r]
 // (u8 [B][S][S]; null: ones); the other families read image r and take no mask.
-// rows: the last block and the final norm on the listed quads only; `tokens` then receives the 4 rows->nq compact rows [.][D].
+// rows: the last block, the final norm and (CLIP) the head on the listed quads only; `tokens` then receives the 4 rows->nq compact rows
+// [.][Dout].
 static int vit_forward_impl(pio_handle c, const float* imgs, int32_t B, const int32_t* img_of_region, const uint8_t* masks, float* tokens,
                             float* qkv_last, hipStream_t s, const RowSel* rows = nullptr) {
   const int D = c->D, M = B * c->Tp;
@@ -1248,6 +1250,13 @@ static int vit_forward_impl(pio_handle c, const float* imgs, int32_t B, const in
   }
   if (rows) {     // final norm of the compact rows, row i -> tokens[i] (one "image" of 4 nq rows: nothing is dropped or moved)
     const int Mt = 4 * rows->nq;
+    if (c->vhead_w) {
+      // CLIP: ln_post into the fp32 scratch (Mt <= xs_rows <= max_batch * T rows), then the head with M = Mt -> tokens [Mt][Dout].  A row
+      // of k_sgemm_tn's output is a function of its A row alone (K ascending in chunks of 32, no split-K): the dense head's bits
+      HIP_OK(launch_layernorm(c->op, c->xs, c->norm_w, c->norm_b, c->cfg.vit_ln_eps, Mt, D, nullptr, c->tok_tmp, Mt, Mt, s));
+      HIP_OK(launch_sgemm_tn(c->tok_tmp, D, c->vhead_w, D, nullptr, 1.f, tokens, c->Dout, Mt, c->Dout, D, 0, 0, s));
+      return PIO_OK;
+    }
     HIP_OK(launch_layernorm(c->op, c->xs, c->norm_w, c->norm_b, c->cfg.vit_ln_eps, Mt, D, nullptr, tokens, Mt, Mt, s));
     return PIO_OK;
   }
@@ -1275,8 +1284,8 @@ int pio_vit_forward_rows(pio_handle c, const float* imgs, int32_t B, const int32
                          float* tokens, int32_t* row_map, pio_stream stream) {
   if (!c || !imgs || !tokens || !quads_host || !img_off_host || !row_map) return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward_rows: null argument");
   if (!c->has_vit) return fail(PIO_ERR_NOT_READY, "pio_vit_forward_rows: backbone weights not loaded");
-  if (c->cfg.vit_arch != 0 || c->vit_f32 || !c->xs)
-    return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward_rows: the fp16 / bf16 DINOv2 ViT only (call pio_vit_forward)");
+  if (c->cfg.vit_arch > 1 || c->cfg.vit_self_only_layers != 0 || c->vit_f32 || !c->xs)
+    return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward_rows: the fp16 / bf16 DINOv2 ViT and the CLIP ViT without self-only blocks only (call pio_vit_forward)");
   if (!PIO_ROWS_LINKED) return fail(PIO_ERR_NOT_READY, "pio_vit_forward_rows: the row-selection kernels are not linked");
   if (B < 1 || B > c->cfg.max_batch) return fail(PIO_ERR_CAPACITY, "pio_vit_forward_rows: batch above max_batch");
   RowSel r;
@@ -1297,11 +1306,23 @@ int pio_vit_forward_rows(pio_handle c, const float* imgs, int32_t B, const int32
   return vit_forward_impl(c, imgs, B, nullptr, nullptr, tokens, nullptr, s, &r);
 }
 
+// Grids above the 1536 cells the region kernels held before this tower existed are opened for the plain CLIP ViT only (vit_arch 1:
+// DenseCLIP's 40 x 40 patches at 640^2).  For every other family the refusal above 1536 cells is behaviour that a test pins
+// (a DINOv2 engine at 560^2), and it stays: lifting it there is a change of its own.
+static bool region_grid_ok(const pio_context* c) {
+  return c->n2 <= (c->cfg.vit_arch == 1 ? kRegionMaxCells : kRegionLegacyCells);
+}
+#define REGION_GRID_OK(c, who)                                                                                                      \
+  if (!region_grid_ok(c))                                                                                                           \
+  return fail(PIO_ERR_SHAPE, std::string(who) + ": a grid of " + std::to_string((c)->n) + " x " + std::to_string((c)->n) +          \
+                                 " is above the cells the region kernels serve for this tower (1536; 1792 for the CLIP ViT)")
+
 int pio_region_reduce_rows(pio_handle c, const float* tokens, const int32_t* row_map, const float* weights, const int32_t* img_index,
                            int32_t R, float scale, float* out, pio_stream stream) {
   if (!c || !tokens || !row_map || !weights || !out) return fail(PIO_ERR_INVALID_ARG, "pio_region_reduce_rows: null argument");
   if (R < 1) return fail(PIO_ERR_INVALID_ARG, "pio_region_reduce_rows: empty input");
   if (!PIO_ROWS_LINKED) return fail(PIO_ERR_NOT_READY, "pio_region_reduce_rows: the row-selection kernels are not linked");
+  REGION_GRID_OK(c, "pio_region_reduce_rows");
   HIP_OK(hipSetDevice(c->cfg.device));
   HIP_OK(launch_region_reduce_rows(tokens, row_map, c->Dout, c->n2, weights, img_index, R, scale, out, (hipStream_t)stream));
   return PIO_OK;
@@ -1376,6 +1397,7 @@ int pio_cls_attention(pio_handle c, const float* qkv_last, const float* tokens, 
   if (c->cfg.vit_arch >= 1) return fail(PIO_ERR_INVALID_ARG, "pio_cls_attention: the CLIP ViT exposes no qkv hook (has_attention = False, P/src/model.py:864-865)");
   if (B < 1 || B > c->cfg.max_batch) return fail(PIO_ERR_CAPACITY, "pio_cls_attention: batch above max_batch");
   if ((avg_token || disentangled) && !tokens) return fail(PIO_ERR_INVALID_ARG, "pio_cls_attention: tokens required");
+  if (avg_token || disentangled) { REGION_GRID_OK(c, "pio_cls_attention"); }
   HIP_OK(hipSetDevice(c->cfg.device));
   hipStream_t s = (hipStream_t)stream;
   const int Hr = c->cfg.readout_heads;
@@ -1408,6 +1430,7 @@ int pio_bbox_weights(pio_handle c, const int32_t* boxes, int32_t B, int32_t NB, 
   if (B < 1 || NB < 1) return fail(PIO_ERR_INVALID_ARG, "pio_bbox_weights: empty batch");
   if (mode < 0 || mode > 3) return fail(PIO_ERR_INVALID_ARG, "pio_bbox_weights: mode must be 0..3");
   if (mode == 1 && !(variance > 0.f)) return fail(PIO_ERR_INVALID_ARG, "pio_bbox_weights: gaussian mode needs variance > 0");
+  REGION_GRID_OK(c, "pio_bbox_weights");
   HIP_OK(hipSetDevice(c->cfg.device));
   HIP_OK(launch_bbox_weights(boxes, B, NB, c->n, mode, variance, center_choice, attn, weights, single_map, single,
                              (hipStream_t)stream));
@@ -1419,6 +1442,7 @@ int pio_region_reduce(pio_handle c, const float* tokens, int32_t B, const float*
   if (!c || !tokens || !weights || !out) return fail(PIO_ERR_INVALID_ARG, "pio_region_reduce: null argument");
   if (R < 1 || B < 1) return fail(PIO_ERR_INVALID_ARG, "pio_region_reduce: empty input");
   if (!img_index && R > B) return fail(PIO_ERR_INVALID_ARG, "pio_region_reduce: img_index required when R > B");
+  REGION_GRID_OK(c, "pio_region_reduce");
   HIP_OK(hipSetDevice(c->cfg.device));
   HIP_OK(launch_region_reduce(tokens, c->T, c->G, c->Dout, c->n2, weights, img_index, R, scale, out, (hipStream_t)stream));
   return PIO_OK;
@@ -1427,6 +1451,7 @@ int pio_region_reduce(pio_handle c, const float* tokens, int32_t B, const float*
 int pio_gaussian_map(pio_handle c, float variance, float* map, pio_stream stream) {
   if (!c || !map) return fail(PIO_ERR_INVALID_ARG, "pio_gaussian_map: null argument");
   if (!(variance > 0.f)) return fail(PIO_ERR_INVALID_ARG, "pio_gaussian_map: variance must be > 0 (0 = host-drawn one-hot)");
+  REGION_GRID_OK(c, "pio_gaussian_map");
   HIP_OK(hipSetDevice(c->cfg.device));
   HIP_OK(launch_gaussian_map(c->n, variance, map, (hipStream_t)stream));
   return PIO_OK;

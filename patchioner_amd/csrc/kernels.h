@@ -184,6 +184,14 @@ hipError_t launch_cls_logits(const float* qkv_last, int B, int T, int G, int D, 
                              float* mean_logits, float* head_logits, hipStream_t s);
 hipError_t launch_softmax_rows(const float* in, float* out, int rows, int n, hipStream_t s);
 hipError_t launch_trace_grids(const double* xy, const int32_t* offsets, int B, int n, float* grids, hipStream_t s);
+// The largest grid the region kernels (k_region_reduce, k_bbox_weights, k_gaussian_map) hold: kRegionCellsPerThread cells per thread of a
+// 256-thread workgroup, 1792 cells = a grid of 42 (the 40 x 40 patches of a ViT-B/16 at 640^2 included).  A thread adds its cells in
+// index order, so a grid of at most 1536 cells gets the sums it got with 6 cells per thread, bit for bit: its 7th term is an exact + 0.
+// kRegionLegacyCells: what they held before, and what every tower family but the plain CLIP ViT is still served up to (api.cpp,
+// region_grid_ok).
+static constexpr int kRegionCellsPerThread = 7;
+static constexpr int kRegionMaxCells = 256 * kRegionCellsPerThread;
+static constexpr int kRegionLegacyCells = 1536;
 hipError_t launch_bbox_weights(const int32_t* boxes, int B, int NB, int n, int mode, float variance,
                                const int32_t* center_choice, float* attn, float* weights, int single_map,
                                float* single, hipStream_t s);

@@ -81,13 +81,13 @@ __global__ __launch_bounds__(256) void k_region_reduce(const float* __restrict__
                                                        float scale, float* out, const int32_t* __restrict__ row_map) {
   // grid (R, ceil(D/256)): lane = one float4 column of a 256-channel slab; the 4 waves split the patches
   // (p = wave, wave+4, ...) with the weight row staged in LDS, then meet in LDS.
-  __shared__ float s_w[1536];
+  __shared__ float s_w[kRegionMaxCells];
   __shared__ __attribute__((aligned(16))) float s_acc[4][256];
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int img = img_index ? img_index[r] : r;
   // row_map: compact tokens (the sparse last block), patch p of the image is row rm[p], staged beside the weights; else the dense
   // [B][T][D] layout
-  __shared__ int32_t s_rm[1536];
+  __shared__ int32_t s_rm[kRegionMaxCells];
   const int32_t* rm = row_map ? row_map + (size_t)img * n2 : nullptr;
   for (int p = tid; p < n2; p += 256) {
     s_w[p] = w[(size_t)r * n2 + p];
@@ -177,10 +177,10 @@ __global__ __launch_bounds__(256) void k_bbox_weights(const int32_t* __restrict_
     py_slice(x1, x1 + w + 1, n, xs, xe);
     const int hs = ye - ys, ws = xe - xs;
     const bool empty = hs * ws == 0;
-    float local[6];                                      // n2 <= 1536 cells per image
+    float local[kRegionCellsPerThread];                        // n2 <= kRegionMaxCells cells per image
     float part = 0.f;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
+    for (int i = 0; i < kRegionCellsPerThread; ++i) {
       const int c = tid + 256 * i;
       float v = 0.f;
       if (c < n2) {
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void k_bbox_weights(const int32_t* __restrict_
     // uniform: ones/(hs*ws); gaussian & attention: w / w.sum(); one-hot: as is
     const float inv = (mode == 2) ? 1.0f : 1.0f / sum;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
+    for (int i = 0; i < kRegionCellsPerThread; ++i) {
       const int c = tid + 256 * i;
       if (c < n2) {
         const int cy = c / n, cx = c - cy * n;
@@ -231,10 +231,10 @@ __global__ __launch_bounds__(256) void k_bbox_weights(const int32_t* __restrict_
 __global__ __launch_bounds__(256) void k_gaussian_map(int n, float variance, float* map) {
   __shared__ float red[4];
   const int tid = threadIdx.x, n2 = n * n;
-  float local[6];
+  float local[kRegionCellsPerThread];
   float part = 0.f;
 #pragma unroll
-  for (int i = 0; i < 6; ++i) {
+  for (int i = 0; i < kRegionCellsPerThread; ++i) {
     const int c = tid + 256 * i;
     float v = 0.f;
     if (c < n2) {
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void k_gaussian_map(int n, float variance, flo
   }
   const float sum = block_sum256(part, red);
 #pragma unroll
-  for (int i = 0; i < 6; ++i) {
+  for (int i = 0; i < kRegionCellsPerThread; ++i) {
     const int c = tid + 256 * i;
     if (c < n2) map[c] = variance >= 100.f ? 1.0f / (float)n2 : local[i] / sum;
   }
@@ -280,7 +280,7 @@ hipError_t launch_trace_grids(const double* xy, const int32_t* offsets, int B, i
 hipError_t launch_bbox_weights(const int32_t* boxes, int B, int NB, int n, int mode, float variance,
                                const int32_t* center_choice, float* attn, float* weights, int single_map,
                                float* single, hipStream_t s) {
-  if (n * n > 1536 || mode < 0 || mode > 3) return hipErrorInvalidValue;
+  if (n * n > kRegionMaxCells || mode < 0 || mode > 3) return hipErrorInvalidValue;
   if (mode == 2 && center_choice == nullptr) return hipErrorInvalidValue;
   if (mode == 3 && attn == nullptr) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_bbox_weights, dim3(B), dim3(256), 0, s, boxes, NB, n, mode, variance, center_choice, attn,
@@ -290,7 +290,7 @@ hipError_t launch_bbox_weights(const int32_t* boxes, int B, int NB, int n, int m
 
 hipError_t launch_region_reduce(const float* tokens, int T, int G, int D, int n2, const float* weights,
                                 const int32_t* img_index, int R, float scale, float* out, hipStream_t s) {
-  if (D % 4 != 0 || D > 1024 || R <= 0 || n2 > 1536) return hipErrorInvalidValue;
+  if (D % 4 != 0 || D > 1024 || R <= 0 || n2 > kRegionMaxCells) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_region_reduce, dim3(R, ceil_div(D, 256)), dim3(256), 0, s, tokens, T, G, D, n2, weights, img_index, scale, out,
                      (const int32_t*)nullptr);
   return hipGetLastError();
@@ -298,14 +298,14 @@ hipError_t launch_region_reduce(const float* tokens, int T, int G, int D, int n2
 
 hipError_t launch_region_reduce_rows(const float* tokens, const int32_t* row_map, int D, int n2, const float* weights,
                                      const int32_t* img_index, int R, float scale, float* out, hipStream_t s) {
-  if (D % 4 != 0 || D > 1024 || R <= 0 || n2 > 1536 || row_map == nullptr) return hipErrorInvalidValue;
+  if (D % 4 != 0 || D > 1024 || R <= 0 || n2 > kRegionMaxCells || row_map == nullptr) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_region_reduce, dim3(R, ceil_div(D, 256)), dim3(256), 0, s, tokens, 0, 0, D, n2, weights, img_index, scale, out,
                      row_map);
   return hipGetLastError();
 }
 
 hipError_t launch_gaussian_map(int n, float variance, float* map, hipStream_t s) {
-  if (n * n > 1536 || !(variance > 0.f)) return hipErrorInvalidValue;
+  if (n * n > kRegionMaxCells || !(variance > 0.f)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_gaussian_map, dim3(1), dim3(256), 0, s, n, variance, map);
   return hipGetLastError();
 }

@@ -32,7 +32,7 @@ class Engine:
                  max_batch: int = 16, max_prefixes: int = 64, max_steps: int = 30, vit_dtype: str = "fp16",
                  device_index: int = 0, readout_heads: int = 16, readout_scale: float = 0.125, vit_arch: str = "dinov2",
                  vit_out_dim: int = 0, vit_ln_eps: float = 1e-6, rn_layers=(0, 0, 0, 0), rn_width: int = 0,
-                 rn_attnpool_spatial: bool = True, vit_self_only_layers: int = 0):
+                 rn_attnpool_spatial: bool = True, vit_self_only_layers: int = 0, sparse_clip_tail: bool = False):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise PioError(-101, "no HIP device visible: the captioning path has no CPU fallback")
@@ -65,8 +65,10 @@ class Engine:
         self._finalized = False
         self._stage_ring = [dict(host=None, dev=None, event=None) for _ in range(8)]
         self.Tp = (self.T + 7) // 8 * 8          # padded rows per image of the token matrix
-        # the sparse last block (pio_vit_forward_rows): fp16 / bf16 DINOv2 towers
-        self.sparse_ok = vit_arch == "dinov2" and vit_dtype in ("fp16", "bf16") and not vit_self_only_layers
+        # the sparse last block (pio_vit_forward_rows): fp16 / bf16 DINOv2 towers; the plain CLIP ViT (no self-only block), whose tail is
+        # the last block, ln_post and the head, only when the caller asks for it (sparse_clip_tail)
+        self.sparse_ok = (vit_dtype in ("fp16", "bf16") and not vit_self_only_layers
+                          and (vit_arch == "dinov2" or (vit_arch == "clip" and bool(sparse_clip_tail))))
         self._stage_next = 0
 
     def close(self):

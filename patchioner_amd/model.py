@@ -6,15 +6,20 @@ attributes (``image_transforms``, ``image_transforms_no_crop``, ``resize_dim``, 
 drivers run unchanged.  Everything numerical is a C-ABI call into libpatchioner_hip.so; there is no CPU
 path (constructing the model without a GPU or without the built library raises).
 
-Scope: the DINOv2(+registers), timm OpenAI-CLIP, AlphaCLIP, RegionCLIP and INViTE backbones with the
-DeCap / CapDec and ViECap heads.  The other backbones and heads of the reference (ProxyCLIP, DenseClip, OpenCLIP, DINO.txt,
-MeaCap, ClipCap) raise ``NotImplementedError`` or ``ValueError`` at construction.
+Scope: the DINOv2(+registers), timm OpenAI-CLIP, AlphaCLIP, RegionCLIP, INViTE and DenseCLIP backbones with the
+DeCap / CapDec, ViECap and ClipCap (MLP mapper) heads.  The other backbones and heads of the reference (ProxyCLIP, OpenCLIP, DINO.txt,
+MeaCap) raise ``NotImplementedError`` or ``ValueError`` at construction.
 
 Build-specific config keys (there is no network on the target, so nothing is fetched from torch.hub / HF):
   dino_weights     path (.pt/.pth state dict) or dict of the DINOv2 backbone weights
   memory_bank      path (.npy / .pt / .h5) or tensor [M, D] of the text memory bank
   synthetic_seed   int: synthesise any weights / bank not given (seeded; see weights.py)
   max_batch, max_prefixes, vit_dtype ("fp16" | "bf16")
+  denseclip_config   a dict of the DenseCLIP YAML's structure, a .yaml path, or a config name (denseclip.py); denseclip_config_dir: where
+                   names are looked up (else $PIO_DENSECLIP_CONFIG_DIR, else the two built-in names); denseclip_checkpoint: a local
+                   checkpoint file or {'state_dict': ...} that replaces the config's checkpoint.path
+  sparse_last_block  None (default): traces-only calls run the last block on the rows the traces read on the DINOv2 and DenseCLIP
+                   backbones; True: on the timm-CLIP and INViTE (extract_last_k_th_token <= 0) towers as well; False: never
   clip_text_weights  path (clip.load JIT archive or state dict) or dict of the CLIP text tower that encodes
                    ``online_texts`` (clip_text.py).  Order of the sources: this key, ~/.cache/clip/<name>.pt (where clip.load
                    puts it), synthetic_seed, else FileNotFoundError
@@ -39,7 +44,7 @@ from .engine import Engine
 from .preprocess import make_transforms
 from .tokenizer import ClipDetokenizer
 
-_OUT_OF_SCOPE = ("proxyclip_clipmodel", "denseclip_config")
+_OUT_OF_SCOPE = ("proxyclip_clipmodel",)
 
 
 def _load_state_dict(spec):
@@ -185,6 +190,69 @@ def _invite_setup(ic: dict, resize_dim: int, crop_dim: int, synthetic_seed) -> d
                 self_only=0 if k <= 0 else min(k, layers))              # clipfolder/model.py:216-217: k >= layers masks every block
 
 
+_DENSECLIP_BLOCKED_NAMES = ("dinov2", "patch16", "patch14", "patch32", "openai")
+
+
+def _denseclip_routed(dino_model, denseclip_config, regionclip_config=None, invite_config=None) -> bool:
+    """Does the reference's constructor reach its DenseClip branches (P/src/model.py:200-235, 254-304, 338-513, 584-610)?  Only with a
+    dino_model (:200, :338), one that none of the name tests in front of it takes ('dinov2', 'patch16', 'patch14', 'patch32' at :201-208,
+    'dinov2' / 'openai' at :339-358), and with regionclip_config and invite_config both None (:214-217, :427, :459: both are tested
+    first).  The YAML says 'INViTE_B16'.  A name that wins leaves denseclip_config unread."""
+    return (denseclip_config is not None and dino_model is not None and regionclip_config is None and invite_config is None
+            and not any(t in dino_model for t in _DENSECLIP_BLOCKED_NAMES))
+
+
+def _denseclip_setup(dc, crop_dim: int, synthetic_seed, online_texts, config_dir=None, checkpoint=None) -> dict:
+    """DenseCLIP's CLIP ViT (P/src/model.py:230-234, 277-283, 302-304, 487-513, 639-641; denseclip/loader.py:19-33;
+    clip_loader/denseclip_loader.py:35-49, 196-227, 230-316): resolves the config (denseclip.resolve_config), loads the checkpoint and
+    returns the engine's weights with the tower's sizes and the attributes the reference derives.  The checkpoint is, in this order:
+    ``checkpoint`` (this build's override: a local file or a {'state_dict': ...} dict), the config's ``checkpoint.path`` (a dict-form
+    config may put the {'state_dict': ...} dict itself under ``checkpoint``), synthetic weights from synthetic_seed when that path does
+    not exist.  Everything is checked before the device is touched."""
+    from . import denseclip as DC
+    if online_texts is not None:
+        raise NotImplementedError("online_texts with DenseCLIP: the bank would come from DenseCLIP's own text tower and tokenizer, which "
+                                  "this build does not implement; pass the bank as a file or tensor (memory_bank)")
+    cfg = DC.resolve_config(dc, config_dir)
+    vis_cfg = (cfg.get('model') or {}).get('vision') or {}
+    patch_size = vis_cfg.get('vision_patch_size', 16)                               # model.py:234, 513
+    embed_dim = vis_cfg.get('embed_dim', 512)                                       # model.py:283, 304
+    vision = DC.vision_block(cfg)                                                   # DenseCLIPModel.__init__ indexes all five
+    res, tower_patch = vision["image_resolution"], vision["vision_patch_size"]
+    n = res // tower_patch
+    if crop_dim // tower_patch != n or crop_dim % tower_patch != 0:
+        # clip_loader/models.py:147, 161: the position table is built for image_resolution; the add fails for any other crop
+        raise RuntimeError("The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 1: the DenseCLIP "
+                           "tower is built for %d x %d inputs (denseclip_config model.vision.image_resolution)"
+                           % ((crop_dim // tower_patch) ** 2 + 1, n * n + 1, res, res))
+    ck = checkpoint
+    explicit = ck is not None
+    if ck is None:
+        ck = cfg.get('checkpoint')
+        if isinstance(ck, dict) and 'state_dict' not in ck and 'path' in ck:
+            ck = ck['path']
+        explicit = isinstance(ck, dict)
+    if isinstance(ck, (str, os.PathLike)):
+        if not os.path.exists(ck):
+            if explicit or synthetic_seed is None:
+                # the reference prints "Checkpoint not found ... using random weights" and captions with a random tower
+                raise FileNotFoundError("DenseCLIP checkpoint %r not found: the reference would go on with RANDOM weights "
+                                        "(denseclip_loader.py:281-282); give a local file or state dict (denseclip_checkpoint, or the "
+                                        "config's checkpoint.path), or synthetic_seed" % (os.fspath(ck),))
+            ck = W.synth_denseclip_vit(synthetic_seed + 1, res, vision["vision_layers"], vision["vision_width"], tower_patch,
+                                       vision["embed_dim"])
+        else:
+            ck = torch.load(ck, map_location="cpu")
+    elif ck is None:
+        if synthetic_seed is None:
+            raise FileNotFoundError("denseclip_config has no checkpoint.path and no denseclip_checkpoint was given (or synthetic_seed)")
+        ck = W.synth_denseclip_vit(synthetic_seed + 1, res, vision["vision_layers"], vision["vision_width"], tower_patch,
+                                   vision["embed_dim"])
+    sd = W.denseclip_to_engine(ck, vision)
+    return dict(sd=sd, cfg=cfg, width=vision["vision_width"], layers=vision["vision_layers"], heads=vision["vision_width"] // 64,
+                patch_size=patch_size, out_dim=vision["embed_dim"], embed_dim=embed_dim, resolution=res)
+
+
 class Patchioner(nn.Module):
 
     def __init__(self, decoder_weights, device, prefix_size, linear_talk2dino, support_memory_size, projection_type=None,
@@ -195,9 +263,10 @@ class Patchioner(nn.Module):
                  denseclip_config=None, alphaclip_config=None, clipcap_config=None, hf_repo_id=None,
                  dino_weights=None, memory_bank=None, synthetic_seed=None, max_batch=16, max_prefixes=128,
                  vit_dtype="fp16", memory_bank_texts=None, clip_text_weights=None, clip_text_dtype="fp16",
-                 talk2dino_projection_weights=None, **kwargs):
+                 talk2dino_projection_weights=None, denseclip_config_dir=None, denseclip_checkpoint=None, sparse_last_block=None,
+                 **kwargs):
         super().__init__(**kwargs)
-        given = dict(proxyclip_clipmodel=proxyclip_clipmodel, denseclip_config=denseclip_config)
+        given = dict(proxyclip_clipmodel=proxyclip_clipmodel)
         for k in _OUT_OF_SCOPE:
             if given[k] is not None:
                 raise NotImplementedError("%s: backbone/head outside the MI355X hot-path scope (DINOv2 + DeCap/CapDec)" % k)
@@ -216,7 +285,15 @@ class Patchioner(nn.Module):
         is_alpha = alphaclip_config is not None
         is_region = regionclip_config is not None
         is_invite = invite_config is not None and not is_region       # model.py:214-217: regionclip_config is tested first
+        if denseclip_config is not None and (is_region or invite_config is not None):
+            raise NotImplementedError("denseclip_config beside regionclip_config / invite_config: the reference tests those two first "
+                                      "(P/src/model.py:214-230) and never reads the DenseCLIP config; give one backbone config")
+        # model.py:230, 487: denseclip_config is tested after regionclip_config and invite_config and before alphaclip_config
+        is_dense = _denseclip_routed(dino_model, denseclip_config, regionclip_config, invite_config)
         alpha_sd = None
+        if is_dense:
+            dn = _denseclip_setup(denseclip_config, crop_dim, synthetic_seed, online_texts, denseclip_config_dir, denseclip_checkpoint)
+            is_alpha = False
         if is_region:
             rn = _regionclip_setup(regionclip_config, dino_model, crop_dim, synthetic_seed, online_texts)
         if is_invite:
@@ -244,7 +321,7 @@ class Patchioner(nn.Module):
         # P/src/model.py:339-392: 'dinov2' names load from torch.hub, 'openai' names are the timm OpenAI-CLIP towers of the
         # "DeCap original" configurations (configs/decap_B16*.k.yaml, decap_B32.k.yaml)
         is_clip = dino_model is not None and 'openai' in dino_model and 'dinov2' not in dino_model
-        if is_alpha or is_region or is_invite:
+        if is_alpha or is_region or is_invite or is_dense:
             pass
         elif dino_model is None or 'dinotxt' in dino_model or not ('dinov2' in dino_model or is_clip):
             raise ValueError("Unsupported backbone %r: this build implements the DINOv2 ViT-S/B/L-14 family and the timm "
@@ -279,13 +356,15 @@ class Patchioner(nn.Module):
 
         self.normalize = normalize
         # traces-only calls run the backbone's last block on the rows the traces read (forward, TraceCaptionPipeline); False: always dense
-        self.sparse_last_block = True
+        # (sparse_last_block=None: on, for the backbones that take it by default -- DINOv2 and DenseCLIP; True: the timm-CLIP and INViTE
+        # extract_last_k_th_token <= 0 towers as well, whose launches are otherwise exactly what they were)
+        self.sparse_last_block = sparse_last_block is None or bool(sparse_last_block)
         self.resize_dim = resize_dim
         self.crop_dim = crop_dim
         self.model_name = dino_model
         # RegionCLIP: 5, as the reference's `"reg" in dino_model` makes it for 'regionclip_*' names (model.py:198) -- read only by the
         # attention read-out, which this backbone never reaches; its tokens are 1 cls row + n^2 patches (self._G)
-        self.num_global_tokens = 1 if is_alpha or is_invite or dino_model is None or "reg" not in dino_model else 5
+        self.num_global_tokens = 1 if is_alpha or is_invite or is_dense or dino_model is None or "reg" not in dino_model else 5
         self._G = 1 if is_region else self.num_global_tokens
         if is_region:
             # model.py:214-216, 254-263: patch_size and embed_dim come from the config; the tokens are the attnpool's output width
@@ -301,6 +380,11 @@ class Patchioner(nn.Module):
             # model.py:217-229, 291-301: patch_size and embed_dim from the model NAME; the tokens are ln_post(x) @ proj wide
             depth, heads, patch_size, self.token_dim = iv["layers"], iv["heads"], iv["patch_size"], iv["out_dim"]
             self.embed_dim = iv["embed_dim"]
+        elif is_dense:
+            # model.py:230-234, 277-283, 302-304: patch_size and embed_dim from the config; the tokens are ln_post(x) @ proj wide
+            depth, heads, patch_size, self.token_dim = dn["layers"], dn["heads"], dn["patch_size"], dn["out_dim"]
+            self.embed_dim = dn["embed_dim"]
+            self.denseclip_config = dn["cfg"]                     # model.py:641: the dict copy
         elif is_clip:
             # timm VisionTransformer with pre_norm, nn.LayerNorm (eps 1e-5), QuickGELU (model.py:363-371); the reference hands
             # img_size=resize_dim to timm, which resamples the checkpoint's position table for any size but 224 at load
@@ -314,11 +398,11 @@ class Patchioner(nn.Module):
             raise ValueError("crop_dim must be a multiple of %d (the reference's reshape fails otherwise)" % patch_size)
         self.num_patch_tokens = crop_dim // patch_size * crop_dim // patch_size
         self.num_tokens = self.num_global_tokens + self.num_patch_tokens
-        self.num_attn_heads = 16 if is_alpha or is_region or is_invite or 'vits' not in dino_model else 6
+        self.num_attn_heads = 16 if is_alpha or is_region or is_invite or is_dense or 'vits' not in dino_model else 6
         self.scale = 0.125
         self.patch_size = patch_size
-        self.backbone_type = 'RegionCLIP' if is_region else ('INViTE' if is_invite else ('AlphaClip' if is_alpha else ('CLIP' if is_clip else 'DINO')))  # model.py:634-651
-        if is_clip or is_alpha or is_region or is_invite:
+        self.backbone_type = 'RegionCLIP' if is_region else ('INViTE' if is_invite else 'DenseClip' if is_dense else ('AlphaClip' if is_alpha else ('CLIP' if is_clip else 'DINO')))  # model.py:634-651
+        if is_clip or is_alpha or is_region or is_invite or is_dense:     # DenseClip: model.py:497-510
             from .preprocess import CLIP_MEAN, CLIP_STD
             self.image_transforms, self.image_transforms_no_crop = make_transforms(resize_dim, crop_dim, CLIP_MEAN, CLIP_STD)
             if is_invite:
@@ -328,7 +412,7 @@ class Patchioner(nn.Module):
         else:
             self.image_transforms, self.image_transforms_no_crop = make_transforms(resize_dim, crop_dim)
 
-        vit_sd = rn["sd"] if is_region else (iv["sd"] if is_invite else (alpha_sd if is_alpha else _load_state_dict(dino_weights)))
+        vit_sd = rn["sd"] if is_region else (iv["sd"] if is_invite else dn["sd"] if is_dense else (alpha_sd if is_alpha else _load_state_dict(dino_weights)))
         if vit_sd is None:
             if synthetic_seed is None:
                 raise FileNotFoundError("dino_weights is required: torch.hub.load('facebookresearch/dinov2', ...) / "
@@ -336,7 +420,7 @@ class Patchioner(nn.Module):
             vit_sd = W.synth_clip_vit(synthetic_seed + 1, dino_model) if is_clip else W.synth_dinov2(synthetic_seed + 1, dino_model)
         if not is_region:
             depth = 1 + max(int(k.split(".")[1]) for k in vit_sd if k.startswith("blocks."))
-        if attention_type != 'qkv' and not is_clip and not is_alpha and not is_region and not is_invite:
+        if attention_type != 'qkv' and not is_clip and not is_alpha and not is_region and not is_invite and not is_dense:
             # the reference re-orders the last block's fused q|k|v rows (P/src/model.py:569-582)
             vit_sd = dict(vit_sd)
             D = self.embed_dim
@@ -397,15 +481,19 @@ class Patchioner(nn.Module):
                            vit_out_dim=rn["out_dim"], vit_ln_eps=1e-5, rn_layers=rn["layers"], rn_width=rn["width"],
                            rn_attnpool_spatial=rn["spatial_attn"])
         else:
-            clip_like = is_clip or is_alpha or is_invite
-            arch_kw = dict(embed_dim=alpha_dv if is_alpha else (iv["width"] if is_invite else self.embed_dim),
+            clip_like = is_clip or is_alpha or is_invite or is_dense
+            arch_kw = dict(embed_dim=alpha_dv if is_alpha else (iv["width"] if is_invite else dn["width"] if is_dense else self.embed_dim),
                            num_registers=self.num_global_tokens - 1,
                            pretrain_grid=int(math.isqrt(vit_sd["pos_embed"].shape[1] - 1)),
                            vit_arch="alphaclip" if is_alpha else ("clip" if clip_like else "dinov2"),
                            vit_out_dim=self.token_dim if clip_like else 0, vit_ln_eps=1e-5 if clip_like else 1e-6,
                            # INViTE: the tower is the CLIP engine whose last blocks attend to themselves only; its table arrives
                            # at the tower's own grid (weights.invite_to_engine), so the engine resamples nothing
-                           vit_self_only_layers=iv["self_only"] if is_invite else 0)
+                           vit_self_only_layers=iv["self_only"] if is_invite else 0,
+                           # DenseCLIP: the plain CLIP engine on fp32 checkpoint values, its table at its own grid; its traces-only
+                           # calls take the sparse tail (last block, ln_post, head) by default, the other CLIP towers when asked
+                           # (the engine itself keeps towers with self-only blocks, AlphaCLIP and the fp32 mode dense)
+                           sparse_clip_tail=is_dense if sparse_last_block is None else bool(sparse_last_block))
         self.engine = Engine(depth=depth, num_heads=heads, crop_dim=crop_dim, patch_size=patch_size, prefix_size=prefix_size,
                              max_batch=max_batch, max_prefixes=max_prefixes, vit_dtype=vit_dtype,
                              device_index=self._device.index, readout_heads=self.num_attn_heads, readout_scale=self.scale,
@@ -539,6 +627,9 @@ class Patchioner(nn.Module):
             clip_text_weights=config.get('clip_text_weights', None),
             clip_text_dtype=config.get('clip_text_dtype', 'fp16'),
             talk2dino_projection_weights=config.get('talk2dino_projection_weights', None),
+            denseclip_config_dir=config.get('denseclip_config_dir', None),
+            denseclip_checkpoint=config.get('denseclip_checkpoint', None),
+            sparse_last_block=config.get('sparse_last_block', None),
         )
         model.to(device)
         return model

@@ -250,8 +250,11 @@ def synth_invite_vit(seed: int, name: str = "ViT-B/16", depth: int | None = None
     proj [width, output_dim].  fp32 values that are NOT fp16-representable: the loader's rounding (invite_to_engine) is visible.
     Drawn with _cn, so that the checkpoint is the same bits on every host (a fixture of the reference's fp32 tokens is held to 1e-5)."""
     D, full_depth, _, p, out, res = invite_arch(name)
-    depth = depth or full_depth
-    n = res // p
+    return synth_invite_tower(seed, D, depth or full_depth, p, out, res // p)
+
+
+def synth_invite_tower(seed: int, D: int, depth: int, p: int, out: int, n: int) -> Dict[str, torch.Tensor]:
+    """synth_invite_vit's draws for a tower given by its sizes: width D, ``depth`` blocks, patch p, output dim ``out``, grid n."""
     g = torch.Generator().manual_seed(seed)
     w: Dict[str, torch.Tensor] = {}
     w["conv1.weight"] = _cn(g, (D, 3, p, p), 0.02)
@@ -336,6 +339,67 @@ def invite_to_engine(sd: Dict[str, torch.Tensor], resolution: Optional[int] = No
     if resolution is not None and resolution // patch != grid:
         src["positional_embedding"] = invite_resize_pos_embed(vis["positional_embedding"].detach(), resolution // patch).float()
     return _openai_visual_to_engine(src)
+
+
+def denseclip_tower_keys(layers: int):
+    """The parameter names of DenseCLIP's CLIPVisionTransformer with ``layers`` blocks (P/src/denseclip/clip_loader/models.py:138-154)."""
+    keys = ["conv1.weight", "class_embedding", "positional_embedding", "ln_pre.weight", "ln_pre.bias", "ln_post.weight", "ln_post.bias", "proj"]
+    for i in range(layers):
+        q = "transformer.resblocks.%d." % i
+        keys += [q + k for k in ("ln_1.weight", "ln_1.bias", "ln_2.weight", "ln_2.bias", "attn.in_proj_weight", "attn.in_proj_bias",
+                                 "attn.out_proj.weight", "attn.out_proj.bias", "mlp.c_fc.weight", "mlp.c_fc.bias", "mlp.c_proj.weight",
+                                 "mlp.c_proj.bias")]
+    return keys
+
+
+def synth_denseclip_vit(seed: int, resolution: int = 640, depth: int | None = None, width: int = 768, patch: int = 16,
+                        embed_dim: int = 512) -> Dict[str, object]:
+    """A DenseCLIP segmentation checkpoint as load_denseclip_weights reads it (P/src/denseclip/clip_loader/denseclip_loader.py:196-227):
+    ``{'state_dict': {...}}`` with the visual tower under ``backbone.`` (OpenAI's names, the position table at ``resolution``'s grid),
+    beside what the loader must ignore: FPN layers under ``backbone.fpn*``, a ``text_encoder.`` tensor, neck and decode-head tensors.
+    fp32 values that are not fp16-representable (the loader rounds nothing); drawn with _cn, the same bits on every host."""
+    depth = depth or 12
+    tower = synth_invite_tower(seed, width, depth, patch, embed_dim, resolution // patch)
+    g = torch.Generator().manual_seed(seed + 7919)
+    sd: Dict[str, torch.Tensor] = {"backbone." + k: v for k, v in tower.items()}
+    sd["backbone.fpn1.0.weight"] = _cn(g, (width, width, 2, 2), 0.02)
+    sd["backbone.fpn1.0.bias"] = _cn(g, (width,), 0.02)
+    sd["backbone.fpn2.0.weight"] = _cn(g, (width, width, 2, 2), 0.02)
+    sd["text_encoder.positional_embedding"] = _cn(g, (13, 512), 0.01)
+    sd["neck.lateral_convs.0.conv.weight"] = _cn(g, (256, width, 1, 1), 0.02)
+    sd["decode_head.conv_seg.weight"] = _cn(g, (150, 128, 1, 1), 0.02)
+    return {"state_dict": sd}
+
+
+def denseclip_to_engine(ckpt, vision: dict) -> Dict[str, torch.Tensor]:
+    """DenseCLIP's loader (load_denseclip_weights / load_denseclip_model, P/src/denseclip/clip_loader/denseclip_loader.py:196-227,
+    255-270) -> the engine's CLIP keys (``vit_arch = 1``).  ``vision``: the config's model.vision block.
+
+    * the checkpoint is ``{'state_dict': ...}``; its ``backbone.`` keys are the visual tower, ``text_encoder.`` and everything else (neck,
+      decode heads) is not the tower's.  Keys under ``backbone.`` that CLIPVisionTransformer has no parameter for (the FPN layers) are what
+      the reference's strict=False drops;
+    * NOTHING is rounded: the reference never calls convert_weights here, the tower runs the checkpoint's fp32 values;
+    * a tower parameter the checkpoint lacks would stay at its random initial value under strict=False: refused here, ln_post and proj
+      included;
+    * the position table must be the tower's own, (image_resolution / patch)^2 + 1 rows: load_state_dict's size-mismatch RuntimeError
+      (strict=False does not excuse a shape).  It is used at that grid, nothing is resampled."""
+    if not isinstance(ckpt, dict) or "state_dict" not in ckpt:
+        raise ValueError("Checkpoint doesn't contain 'state_dict': a DenseCLIP checkpoint is {'state_dict': {'backbone.*': ..., ...}}")
+    layers, width = int(vision["vision_layers"]), int(vision["vision_width"])
+    patch, res = int(vision["vision_patch_size"]), int(vision["image_resolution"])
+    want = denseclip_tower_keys(layers)
+    vis = {k[len("backbone."):]: v for k, v in ckpt["state_dict"].items() if k.startswith("backbone.")}
+    missing = [k for k in want if k not in vis]
+    if missing:
+        raise KeyError("DenseCLIP checkpoint lacks %d tower tensor(s) under 'backbone.' (first: %s): the reference's strict=False load "
+                       "would leave them at their random initial values" % (len(missing), ", ".join(missing[:4])))
+    rows = (res // patch) ** 2 + 1
+    pe = vis["positional_embedding"]
+    if tuple(pe.shape) != (rows, width):
+        raise RuntimeError("Error(s) in loading state_dict for CLIPVisionTransformer:\n\tsize mismatch for positional_embedding: copying a "
+                           "param with shape torch.Size([%s]) from checkpoint, the shape in current model is torch.Size([%d, %d])."
+                           % (", ".join(str(int(d)) for d in pe.shape), rows, width))
+    return _openai_visual_to_engine({k: vis[k].detach().float() for k in want})
 
 
 def add_outlier_channels(w: Dict[str, torch.Tensor], channels=(7, 300, 611), block: int = 1, gain: float = 4000.0,
