@@ -30,7 +30,6 @@ Build-specific config keys (there is no network on the target, so nothing is fet
 """
 from __future__ import annotations
 
-import math
 import os
 import random
 from typing import List, Optional
@@ -40,22 +39,13 @@ import torch.nn as nn
 import yaml
 
 from . import weights as W
+from .backbones import _load_state_dict, route_backbone
+from .backbones import _denseclip_routed, _denseclip_setup, _invite_setup, _regionclip_setup  # noqa: F401  (their old import path)
 from .engine import Engine
-from .preprocess import make_transforms
+from .preprocess import CLIP_MEAN, CLIP_STD, make_transforms
 from .tokenizer import ClipDetokenizer
 
 _OUT_OF_SCOPE = ("proxyclip_clipmodel",)
-
-
-def _load_state_dict(spec):
-    if spec is None:
-        return None
-    if isinstance(spec, dict):
-        return spec
-    if not os.path.exists(spec):
-        raise FileNotFoundError("checkpoint %r not found (no HuggingFace / torch.hub download on this target)" % (spec,))
-    sd = torch.load(spec, map_location="cpu")
-    return sd.get("state_dict", sd) if isinstance(sd, dict) else sd
 
 
 def load_memory_bank(spec, want_texts: bool = False):
@@ -87,172 +77,6 @@ def _load_memory_bank(spec):
     raise ValueError("unsupported memory bank format: %r" % (spec,))
 
 
-def _regionclip_setup(rc: dict, dino_model, crop_dim: int, synthetic_seed, online_texts) -> dict:
-    """RegionCLIP's ModifiedResNet (P/src/model.py:427-457; regionclip/loader.py:39-231): checks the config, loads the checkpoint
-    (``checkpoint``: a RegionCLIP ``backbone.*`` checkpoint or a CLIP ``visual.*`` dict; else synthetic weights from
-    synthetic_seed) and returns the engine's weights with the tower's sizes.  Everything is checked before the device is touched."""
-    resnets = rc.get('MODEL', {}).get('RESNETS', {})
-    out_features = resnets.get('OUT_FEATURES', ['res4'])          # build_model_with_defaults' default (loader.py:158)
-    if 'res5' not in out_features:
-        raise NotImplementedError("RegionCLIP with OUT_FEATURES %r: without 'res5' the reference returns layer3's stride-16 grid, which "
-                                  "disagrees with its own num_patch_tokens (crop / 32)^2 (clip_backbone.py:278-299)" % (out_features,))
-    if online_texts is not None:
-        raise NotImplementedError("online_texts with RegionCLIP: the bank would come from RegionCLIP's own text tower, which this build "
-                                  "does not implement; pass the bank as a file or tensor (memory_bank)")
-    if rc.get('patch_size', 32) != 32:
-        raise NotImplementedError("regionclip_config patch_size %r: the res5 grid is crop / 32, patch_size must be 32" % (rc['patch_size'],))
-    if crop_dim % 32 != 0:
-        raise ValueError("crop_dim must be a multiple of 32 for the RegionCLIP ResNet")
-    sd = _load_state_dict(rc.get('checkpoint', None)) if rc.get('checkpoint', None) is not None else None
-    res = resnets.get('IMAGE_RESOLUTION', None)
-    if sd is None:
-        if synthetic_seed is None:
-            raise FileNotFoundError("regionclip_config['checkpoint'] is required (or synthetic_seed)")
-        name = rc.get('name') or ("RN50x4" if "50x4" in (dino_model or "") or resnets.get('DEPTH') == 200 else "RN50")
-        sd = W.synth_regionclip_rn(synthetic_seed + 1, name, image_resolution=res or 224)
-    layers, width, grid, out_dim = W.regionclip_layers(sd)
-    embed = 32 * width                        # attnpool width and heads as the reference derives them (clip_backbone.py:198-200, 705)
-    heads = embed // 64
-    if res is None:
-        res = grid * 32
-    s = res // 32
-    pos = None
-    if res / 32 != grid:
-        # build_model_with_defaults (loader.py:200-210) drops the checkpoint's table; the tower keeps AttentionPool2d.__init__'s
-        # unseeded draw randn(s^2 + 1, C) / sqrt(C) (clip_backbone.py:76).  Drawn here from torch's default CPU generator: the reference
-        # draws it after the rest of the model's initialisation, so its own values cannot be replayed bit for bit
-        print("Warning: Removing incompatible positional embedding from checkpoint.")
-        print(f"  Checkpoint spatial size: {grid}x{grid} (for image resolution {grid * 32})")
-        print(f"  Config image resolution: {res} (requires {res // 32}x{res // 32})")
-        pos = torch.randn(s * s + 1, embed) / embed ** 0.5
-    if s != crop_dim // 32:
-        raise RuntimeError("The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 0: the attnpool "
-                           "table is built for IMAGE_RESOLUTION %d" % ((crop_dim // 32) ** 2 + 1, s * s + 1, res))
-    return dict(sd=W.regionclip_to_engine(sd, pos=pos), layers=layers, width=width, embed=embed, heads=heads, out_dim=out_dim,
-                spatial_attn=bool(rc.get('use_attnpool_for_spatial_feats', True)))
-
-
-def _invite_setup(ic: dict, resize_dim: int, crop_dim: int, synthetic_seed) -> dict:
-    """INViTE's CLIP ViT (P/src/model.py:217-229, 264-301, 459-485; INViTE/loader.py; clipfolder/clip.py:94-143, model.py:468-515):
-    checks the config, loads the checkpoint (``checkpoint``: a local file or a state dict, the tower alone or a full CLIP dict; else
-    synthetic weights from synthetic_seed) and returns the engine's weights with the tower's sizes, the name-derived attributes and
-    the number of self-only blocks.  Everything is checked before the device is touched."""
-    if 'name' not in ic:
-        raise KeyError("'name' key is required in config dictionary")               # INViTE/loader.py:44-45
-    name = ic['name']
-    if ic.get('jit', False):
-        raise NotImplementedError("invite_config jit: true loads a TorchScript archive, which has neither extract_last_k_th_token nor "
-                                  "get_all_last; use jit: false")
-    if str(name).startswith('RN'):
-        raise NotImplementedError("invite_config name %r: INViTE's ModifiedResNet towers take no get_all_last argument "
-                                  "(P/src/model.py:821 fails on them); only the ViT towers are implemented" % (name,))
-    if ic.get('viz', False):
-        # ResidualAttentionBlock asks for nn.MultiheadAttentionViz (clipfolder/model.py:178), which torch does not have
-        raise AttributeError("module 'torch.nn' has no attribute 'MultiheadAttentionViz'")
-    # patch_size and embed_dim come from the NAME (model.py:217-229, 291-301), with the reference's defaults for unknown names
-    if 'ViT-B/32' in name:
-        patch_size = 32
-    elif 'ViT-B/16' in name:
-        patch_size = 16
-    elif 'ViT-L/14' in name:
-        patch_size = 14
-    else:
-        print(f"Unknown INViTE model {name}, using default patch size 32")
-        patch_size = 32
-    if 'ViT-L' in name:
-        embed_dim = 768
-    elif 'ViT-B' in name:
-        embed_dim = 512
-    else:
-        print(f"Unknown INViTE model {name}, using default embedding dimension 512")
-        embed_dim = 512
-    sd = _load_state_dict(ic.get('checkpoint', None))
-    if sd is None:
-        if synthetic_seed is None:
-            raise FileNotFoundError("invite_config['checkpoint'] is required (a local CLIP checkpoint or state dict): clip.load(%r) "
-                                    "would download the weights, which needs network this target does not have; or synthetic_seed"
-                                    % (name,))
-        sd = W.synth_invite_vit(synthetic_seed + 1, name)
-    width, layers, heads, tower_patch, out_dim, grid = W.invite_dims(sd)
-    if tower_patch != patch_size:
-        raise ValueError("invite_config name %r gives patch_size %d, the checkpoint's conv1 is %d x %d: the reference would map boxes "
-                         "and traces to a grid the tower does not have" % (name, patch_size, tower_patch, tower_patch))
-    res = ic.get('resolution', None) or tower_patch * grid
-    n = res // tower_patch
-    if crop_dim // tower_patch != n or crop_dim % tower_patch != 0:
-        # clipfolder/model.py:264: the position table is built for `resolution`; the add fails for any other crop
-        raise RuntimeError("The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 1: the %s tower "
-                           "is built for %d x %d inputs (invite_config resolution)" % ((crop_dim // tower_patch) ** 2 + 1, n * n + 1,
-                                                                                        name, res, res))
-    k = int(ic.get('extract_last_k_th_token', -1))
-    return dict(sd=W.invite_to_engine(sd, resolution=res), width=width, layers=layers, heads=heads, patch_size=patch_size,
-                out_dim=out_dim, embed_dim=embed_dim, resolution=res,
-                self_only=0 if k <= 0 else min(k, layers))              # clipfolder/model.py:216-217: k >= layers masks every block
-
-
-_DENSECLIP_BLOCKED_NAMES = ("dinov2", "patch16", "patch14", "patch32", "openai")
-
-
-def _denseclip_routed(dino_model, denseclip_config, regionclip_config=None, invite_config=None) -> bool:
-    """Does the reference's constructor reach its DenseClip branches (P/src/model.py:200-235, 254-304, 338-513, 584-610)?  Only with a
-    dino_model (:200, :338), one that none of the name tests in front of it takes ('dinov2', 'patch16', 'patch14', 'patch32' at :201-208,
-    'dinov2' / 'openai' at :339-358), and with regionclip_config and invite_config both None (:214-217, :427, :459: both are tested
-    first).  The YAML says 'INViTE_B16'.  A name that wins leaves denseclip_config unread."""
-    return (denseclip_config is not None and dino_model is not None and regionclip_config is None and invite_config is None
-            and not any(t in dino_model for t in _DENSECLIP_BLOCKED_NAMES))
-
-
-def _denseclip_setup(dc, crop_dim: int, synthetic_seed, online_texts, config_dir=None, checkpoint=None) -> dict:
-    """DenseCLIP's CLIP ViT (P/src/model.py:230-234, 277-283, 302-304, 487-513, 639-641; denseclip/loader.py:19-33;
-    clip_loader/denseclip_loader.py:35-49, 196-227, 230-316): resolves the config (denseclip.resolve_config), loads the checkpoint and
-    returns the engine's weights with the tower's sizes and the attributes the reference derives.  The checkpoint is, in this order:
-    ``checkpoint`` (this build's override: a local file or a {'state_dict': ...} dict), the config's ``checkpoint.path`` (a dict-form
-    config may put the {'state_dict': ...} dict itself under ``checkpoint``), synthetic weights from synthetic_seed when that path does
-    not exist.  Everything is checked before the device is touched."""
-    from . import denseclip as DC
-    if online_texts is not None:
-        raise NotImplementedError("online_texts with DenseCLIP: the bank would come from DenseCLIP's own text tower and tokenizer, which "
-                                  "this build does not implement; pass the bank as a file or tensor (memory_bank)")
-    cfg = DC.resolve_config(dc, config_dir)
-    vis_cfg = (cfg.get('model') or {}).get('vision') or {}
-    patch_size = vis_cfg.get('vision_patch_size', 16)                               # model.py:234, 513
-    embed_dim = vis_cfg.get('embed_dim', 512)                                       # model.py:283, 304
-    vision = DC.vision_block(cfg)                                                   # DenseCLIPModel.__init__ indexes all five
-    res, tower_patch = vision["image_resolution"], vision["vision_patch_size"]
-    n = res // tower_patch
-    if crop_dim // tower_patch != n or crop_dim % tower_patch != 0:
-        # clip_loader/models.py:147, 161: the position table is built for image_resolution; the add fails for any other crop
-        raise RuntimeError("The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 1: the DenseCLIP "
-                           "tower is built for %d x %d inputs (denseclip_config model.vision.image_resolution)"
-                           % ((crop_dim // tower_patch) ** 2 + 1, n * n + 1, res, res))
-    ck = checkpoint
-    explicit = ck is not None
-    if ck is None:
-        ck = cfg.get('checkpoint')
-        if isinstance(ck, dict) and 'state_dict' not in ck and 'path' in ck:
-            ck = ck['path']
-        explicit = isinstance(ck, dict)
-    if isinstance(ck, (str, os.PathLike)):
-        if not os.path.exists(ck):
-            if explicit or synthetic_seed is None:
-                # the reference prints "Checkpoint not found ... using random weights" and captions with a random tower
-                raise FileNotFoundError("DenseCLIP checkpoint %r not found: the reference would go on with RANDOM weights "
-                                        "(denseclip_loader.py:281-282); give a local file or state dict (denseclip_checkpoint, or the "
-                                        "config's checkpoint.path), or synthetic_seed" % (os.fspath(ck),))
-            ck = W.synth_denseclip_vit(synthetic_seed + 1, res, vision["vision_layers"], vision["vision_width"], tower_patch,
-                                       vision["embed_dim"])
-        else:
-            ck = torch.load(ck, map_location="cpu")
-    elif ck is None:
-        if synthetic_seed is None:
-            raise FileNotFoundError("denseclip_config has no checkpoint.path and no denseclip_checkpoint was given (or synthetic_seed)")
-        ck = W.synth_denseclip_vit(synthetic_seed + 1, res, vision["vision_layers"], vision["vision_width"], tower_patch,
-                                   vision["embed_dim"])
-    sd = W.denseclip_to_engine(ck, vision)
-    return dict(sd=sd, cfg=cfg, width=vision["vision_width"], layers=vision["vision_layers"], heads=vision["vision_width"] // 64,
-                patch_size=patch_size, out_dim=vision["embed_dim"], embed_dim=embed_dim, resolution=res)
-
-
 class Patchioner(nn.Module):
 
     def __init__(self, decoder_weights, device, prefix_size, linear_talk2dino, support_memory_size, projection_type=None,
@@ -282,54 +106,13 @@ class Patchioner(nn.Module):
             raise TypeError("online_texts must be a list of str")
         if online_texts is not None and support_memory_size > 0 and len(online_texts) == 0:
             raise ValueError("online_texts is empty")
-        is_alpha = alphaclip_config is not None
-        is_region = regionclip_config is not None
-        is_invite = invite_config is not None and not is_region       # model.py:214-217: regionclip_config is tested first
-        if denseclip_config is not None and (is_region or invite_config is not None):
-            raise NotImplementedError("denseclip_config beside regionclip_config / invite_config: the reference tests those two first "
-                                      "(P/src/model.py:214-230) and never reads the DenseCLIP config; give one backbone config")
-        # model.py:230, 487: denseclip_config is tested after regionclip_config and invite_config and before alphaclip_config
-        is_dense = _denseclip_routed(dino_model, denseclip_config, regionclip_config, invite_config)
-        alpha_sd = None
-        if is_dense:
-            dn = _denseclip_setup(denseclip_config, crop_dim, synthetic_seed, online_texts, denseclip_config_dir, denseclip_checkpoint)
-            is_alpha = False
-        if is_region:
-            rn = _regionclip_setup(regionclip_config, dino_model, crop_dim, synthetic_seed, online_texts)
-        if is_invite:
-            iv = _invite_setup(invite_config, resize_dim, crop_dim, synthetic_seed)
-            is_alpha = False                                           # model.py:459, 515: invite_config is tested before alphaclip_config
-        if is_alpha:
-            # P/src/model.py:515-545 (alphaclip_loader.load_alphaclip): AlphaCLIP's ViT, the OpenAI-CLIP tower with an alpha input
-            # channel.  Name, crop and weights are checked here, before anything touches the device.
-            alpha_name = alphaclip_config.get('name', None)
-            alpha_dv, _, alpha_heads, alpha_p, alpha_out, alpha_crop = W.alphaclip_arch(alpha_name)
-            if alphaclip_config.get('patch_size', alpha_p) != alpha_p:
-                raise ValueError("alphaclip_config patch_size %r: the %s tower's patches are %d pixels" % (alphaclip_config['patch_size'], alpha_name, alpha_p))
-            if crop_dim != alpha_crop:
-                # alpha_clip/model.py:372: the position table is never resampled, the add fails for any other crop
-                raise RuntimeError("The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 1: the %s "
-                                   "tower takes %d x %d crops" % ((crop_dim // alpha_p) ** 2 + 1, (alpha_crop // alpha_p) ** 2 + 1, alpha_name,
-                                                                   alpha_crop, alpha_crop))
-            alpha_sd = _load_state_dict(alphaclip_config.get('alpha_vision_checkpoint', None))
-            if alpha_sd is None:
-                if synthetic_seed is None:
-                    raise FileNotFoundError("alphaclip_config['alpha_vision_checkpoint'] is required (alpha_clip.load downloads the CLIP "
-                                            "weights, which needs network this target does not have), or synthetic_seed")
-                alpha_sd = W.synth_alphaclip_vit(synthetic_seed + 1, alpha_name)
-            alpha_sd = W.alphaclip_to_engine(alpha_sd)
-        # P/src/model.py:339-392: 'dinov2' names load from torch.hub, 'openai' names are the timm OpenAI-CLIP towers of the
-        # "DeCap original" configurations (configs/decap_B16*.k.yaml, decap_B32.k.yaml)
-        is_clip = dino_model is not None and 'openai' in dino_model and 'dinov2' not in dino_model
-        if is_alpha or is_region or is_invite or is_dense:
-            pass
-        elif dino_model is None or 'dinotxt' in dino_model or not ('dinov2' in dino_model or is_clip):
-            raise ValueError("Unsupported backbone %r: this build implements the DINOv2 ViT-S/B/L-14 family and the timm "
-                             "OpenAI-CLIP ViTs (vit_base_patch16/32_clip_224.openai)" % (dino_model,))
-        if is_clip and not is_alpha and resize_dim != crop_dim:
-            # P/src/model.py:371 builds the tower with img_size=resize_dim: timm's PatchEmbed then asserts that every input is
-            # resize_dim x resize_dim, while the transforms crop to crop_dim -- the reference's first forward fails; fail at once
-            raise AssertionError("Input height (%d) doesn't match model (%d)." % (crop_dim, resize_dim))
+        # the family is decided here and the config-routed towers are set up (backbones.py); the two name-routed towers read their
+        # weights when load_backbone() is called, behind the refusals below, as they always have
+        load_backbone = route_backbone(dino_model=dino_model, regionclip_config=regionclip_config, invite_config=invite_config,
+                                       denseclip_config=denseclip_config, alphaclip_config=alphaclip_config, dino_weights=dino_weights,
+                                       attention_type=attention_type, resize_dim=resize_dim, crop_dim=crop_dim,
+                                       synthetic_seed=synthetic_seed, online_texts=online_texts, denseclip_config_dir=denseclip_config_dir,
+                                       denseclip_checkpoint=denseclip_checkpoint, sparse_last_block=sparse_last_block)
         if viecap_config is not None and viecap_config.get('meacap', False):
             raise NotImplementedError("MeaCap head (retrieved-caption scene graphs, flan-T5): outside the hot-path scope")
         if decoder_weights is None and synthetic_seed is None and not calculate_argmax_text and viecap_config is None and clipcap_config is None:
@@ -362,73 +145,21 @@ class Patchioner(nn.Module):
         self.resize_dim = resize_dim
         self.crop_dim = crop_dim
         self.model_name = dino_model
-        # RegionCLIP: 5, as the reference's `"reg" in dino_model` makes it for 'regionclip_*' names (model.py:198) -- read only by the
-        # attention read-out, which this backbone never reaches; its tokens are 1 cls row + n^2 patches (self._G)
-        self.num_global_tokens = 1 if is_alpha or is_invite or is_dense or dino_model is None or "reg" not in dino_model else 5
-        self._G = 1 if is_region else self.num_global_tokens
-        if is_region:
-            # model.py:214-216, 254-263: patch_size and embed_dim come from the config; the tokens are the attnpool's output width
-            depth, heads, patch_size, self.token_dim = sum(rn["layers"]), rn["heads"], 32, rn["out_dim"]
-            self.embed_dim = regionclip_config.get('embed_dim', 1024)
-            self.regionclip_config = dict(regionclip_config)
-        elif is_alpha:
-            # the tower is alpha_dv wide; the reference's embed_dim is alphaclip_config['embed_dim'] (model.py:305-310), the head's width
-            depth, heads, patch_size, self.token_dim = 0, alpha_heads, alpha_p, alpha_out
-            self.embed_dim = alphaclip_config.get('embed_dim', alpha_out)
-            self.alphaclip_config = dict(alphaclip_config)
-        elif is_invite:
-            # model.py:217-229, 291-301: patch_size and embed_dim from the model NAME; the tokens are ln_post(x) @ proj wide
-            depth, heads, patch_size, self.token_dim = iv["layers"], iv["heads"], iv["patch_size"], iv["out_dim"]
-            self.embed_dim = iv["embed_dim"]
-        elif is_dense:
-            # model.py:230-234, 277-283, 302-304: patch_size and embed_dim from the config; the tokens are ln_post(x) @ proj wide
-            depth, heads, patch_size, self.token_dim = dn["layers"], dn["heads"], dn["patch_size"], dn["out_dim"]
-            self.embed_dim = dn["embed_dim"]
-            self.denseclip_config = dn["cfg"]                     # model.py:641: the dict copy
-        elif is_clip:
-            # timm VisionTransformer with pre_norm, nn.LayerNorm (eps 1e-5), QuickGELU (model.py:363-371); the reference hands
-            # img_size=resize_dim to timm, which resamples the checkpoint's position table for any size but 224 at load
-            # (configs/decap_B16_resize.k.yaml: 592): pio_finalize_weights does the same from the table's own grid
-            self.embed_dim, depth, heads, patch_size, self.token_dim = W.clip_arch(dino_model)
-        else:
-            patch_size = 14
-            self.embed_dim, depth, heads = W.dino_arch(dino_model)
-            self.token_dim = self.embed_dim
-        if crop_dim % patch_size != 0:
-            raise ValueError("crop_dim must be a multiple of %d (the reference's reshape fails otherwise)" % patch_size)
-        self.num_patch_tokens = crop_dim // patch_size * crop_dim // patch_size
+        bb = self._backbone = load_backbone()
+        self.backbone_type = bb.kind
+        self.num_global_tokens, self._G = bb.num_global_tokens, bb.grid_globals
+        self.token_dim, self.embed_dim, self.patch_size = bb.token_dim, bb.embed_dim, bb.patch_size
+        if bb.config is not None:
+            setattr(self, bb.kind.lower() + "_config", bb.config)       # regionclip_config, alphaclip_config, denseclip_config
+        self.num_patch_tokens = crop_dim // bb.patch_size * crop_dim // bb.patch_size
         self.num_tokens = self.num_global_tokens + self.num_patch_tokens
-        self.num_attn_heads = 16 if is_alpha or is_region or is_invite or is_dense or 'vits' not in dino_model else 6
+        self.num_attn_heads = bb.readout_heads
         self.scale = 0.125
-        self.patch_size = patch_size
-        self.backbone_type = 'RegionCLIP' if is_region else ('INViTE' if is_invite else 'DenseClip' if is_dense else ('AlphaClip' if is_alpha else ('CLIP' if is_clip else 'DINO')))  # model.py:634-651
-        if is_clip or is_alpha or is_region or is_invite or is_dense:     # DenseClip: model.py:497-510
-            from .preprocess import CLIP_MEAN, CLIP_STD
-            self.image_transforms, self.image_transforms_no_crop = make_transforms(resize_dim, crop_dim, CLIP_MEAN, CLIP_STD)
-            if is_invite:
-                # model.py:463-473: clip._transform(input_resolution) -- resize AND crop to the tower's resolution, whatever resize_dim
-                # and crop_dim say; the no-crop transform squares to resize_dim
-                self.image_transforms = make_transforms(iv["resolution"], iv["resolution"], CLIP_MEAN, CLIP_STD)[0]
-        else:
-            self.image_transforms, self.image_transforms_no_crop = make_transforms(resize_dim, crop_dim)
-
-        vit_sd = rn["sd"] if is_region else (iv["sd"] if is_invite else dn["sd"] if is_dense else (alpha_sd if is_alpha else _load_state_dict(dino_weights)))
-        if vit_sd is None:
-            if synthetic_seed is None:
-                raise FileNotFoundError("dino_weights is required: torch.hub.load('facebookresearch/dinov2', ...) / "
-                                        "timm.create_model(..., pretrained=True) need network, which this target does not have")
-            vit_sd = W.synth_clip_vit(synthetic_seed + 1, dino_model) if is_clip else W.synth_dinov2(synthetic_seed + 1, dino_model)
-        if not is_region:
-            depth = 1 + max(int(k.split(".")[1]) for k in vit_sd if k.startswith("blocks."))
-        if attention_type != 'qkv' and not is_clip and not is_alpha and not is_region and not is_invite and not is_dense:
-            # the reference re-orders the last block's fused q|k|v rows (P/src/model.py:569-582)
-            vit_sd = dict(vit_sd)
-            D = self.embed_dim
-            wk, bk = "blocks.%d.attn.qkv.weight" % (depth - 1), "blocks.%d.attn.qkv.bias" % (depth - 1)
-            ws = dict(zip("qkv", vit_sd[wk].reshape(3, D, D)))
-            bs = dict(zip("qkv", vit_sd[bk].reshape(3, D)))
-            vit_sd[wk] = torch.cat([ws[x] for x in attention_type], dim=0)
-            vit_sd[bk] = torch.cat([bs[x] for x in attention_type], dim=0)
+        stats = (CLIP_MEAN, CLIP_STD) if bb.clip_stats else (None, None)
+        self.image_transforms, self.image_transforms_no_crop = make_transforms(resize_dim, crop_dim, *stats)
+        if bb.transform_resolution is not None:
+            # the no-crop transform still squares to resize_dim
+            self.image_transforms = make_transforms(bb.transform_resolution, bb.transform_resolution, *stats)[0]
 
         dec_sd = _load_state_dict(decoder_weights)
         if dec_sd is None and synthetic_seed is not None and viecap_config is None:
@@ -476,29 +207,11 @@ class Patchioner(nn.Module):
             dec_kw = dict(dec_layers=n_layer, dec_heads=12, max_steps=256,
                           dec_vocab=int(viecap_sd["gpt.transformer.wte.weight"].shape[0]),
                           dec_positions=int(viecap_sd["gpt.transformer.wpe.weight"].shape[0]))
-        if is_region:
-            arch_kw = dict(embed_dim=rn["embed"], num_registers=0, pretrain_grid=crop_dim // 32, vit_arch="regionclip",
-                           vit_out_dim=rn["out_dim"], vit_ln_eps=1e-5, rn_layers=rn["layers"], rn_width=rn["width"],
-                           rn_attnpool_spatial=rn["spatial_attn"])
-        else:
-            clip_like = is_clip or is_alpha or is_invite or is_dense
-            arch_kw = dict(embed_dim=alpha_dv if is_alpha else (iv["width"] if is_invite else dn["width"] if is_dense else self.embed_dim),
-                           num_registers=self.num_global_tokens - 1,
-                           pretrain_grid=int(math.isqrt(vit_sd["pos_embed"].shape[1] - 1)),
-                           vit_arch="alphaclip" if is_alpha else ("clip" if clip_like else "dinov2"),
-                           vit_out_dim=self.token_dim if clip_like else 0, vit_ln_eps=1e-5 if clip_like else 1e-6,
-                           # INViTE: the tower is the CLIP engine whose last blocks attend to themselves only; its table arrives
-                           # at the tower's own grid (weights.invite_to_engine), so the engine resamples nothing
-                           vit_self_only_layers=iv["self_only"] if is_invite else 0,
-                           # DenseCLIP: the plain CLIP engine on fp32 checkpoint values, its table at its own grid; its traces-only
-                           # calls take the sparse tail (last block, ln_post, head) by default, the other CLIP towers when asked
-                           # (the engine itself keeps towers with self-only blocks, AlphaCLIP and the fp32 mode dense)
-                           sparse_clip_tail=is_dense if sparse_last_block is None else bool(sparse_last_block))
-        self.engine = Engine(depth=depth, num_heads=heads, crop_dim=crop_dim, patch_size=patch_size, prefix_size=prefix_size,
+        self.engine = Engine(depth=bb.depth, num_heads=bb.heads, crop_dim=crop_dim, patch_size=bb.patch_size, prefix_size=prefix_size,
                              max_batch=max_batch, max_prefixes=max_prefixes, vit_dtype=vit_dtype,
                              device_index=self._device.index, readout_heads=self.num_attn_heads, readout_scale=self.scale,
-                             **arch_kw, **dec_kw)
-        self.engine.load_state_dict(vit_sd)
+                             **bb.engine_kw, **dec_kw)
+        self.engine.load_state_dict(bb.state_dict)
         if dec_sd is not None:                         # calculate_argmax_text without decoder weights: no decoder (model.py:165)
             self.engine.load_state_dict(dec_sd)        # strict=False like the reference (decap.py:214)
         if viecap_sd is not None:
@@ -532,7 +245,7 @@ class Patchioner(nn.Module):
             else:
                 raise FileNotFoundError("support_memory_size > 0 needs `memory_bank` (path or tensor): building the "
                                         "bank (CLIP text tower + datasets) is offline work outside this scope")
-            if dino_model is None or 'dinov2' not in dino_model:      # normalize_memory_embs (P/src/model.py:174; im2txtprojection.py:348-349): the CLIP ViTs
+            if bb.normalize_bank:      # normalize_memory_embs (P/src/model.py:174; im2txtprojection.py:348-349): the CLIP ViTs
                 bank = bank / bank.norm(dim=-1, keepdim=True)
             if bank.dim() != 2 or bank.shape[1] != self.token_dim:
                 raise ValueError("memory bank is %s, the %s backbone needs [M, %d]" % (tuple(bank.shape), dino_model, self.token_dim))
@@ -721,7 +434,7 @@ class Patchioner(nn.Module):
         # has_attention (model.py:864-865): only DINO backbones install the qkv hook.  Without it the reference never defines
         # self_attn / avg_self_attn_token / disentangled_self_attn and every option that reads them fails with
         # UnboundLocalError; clean_from == "avg_self_attn" falls back to the cls token (:886-890).
-        has_attention = 'DINO' in self.backbone_type
+        has_attention = self._backbone.has_attention
         if double_DINO_for_bboxes and not has_attention:
             raise AttributeError("double_DINO_for_bboxes re-runs a DINOv2 block (bbox_utils.py:300-403): not a %s backbone" % self.backbone_type)
         tokens, qkv = eng.vit_forward(imgs, want_qkv=has_attention)

@@ -108,7 +108,8 @@ def test_built_in_names_hold_the_shipped_settings(monkeypatch):
 
 # ---- routing -----------------------------------------------------------------------------------------------------------------
 def test_routing_follows_the_references_elif_chains():
-    from patchioner_amd.model import _OUT_OF_SCOPE, _denseclip_routed
+    from patchioner_amd.backbones import _denseclip_routed
+    from patchioner_amd.model import _OUT_OF_SCOPE
     assert _OUT_OF_SCOPE == ("proxyclip_clipmodel",)
     dc = "denseclip_segmentation_vitb16"
     assert _denseclip_routed("INViTE_B16", dc)
@@ -194,7 +195,7 @@ def test_refusals_come_before_the_device_is_touched(tmp_path):
 
 
 def test_setup_attributes_equal_the_references(meta, tmp_path):
-    from patchioner_amd.model import _denseclip_setup
+    from patchioner_amd.backbones import _denseclip_setup
     for tag in TAGS:
         res = DR.TOWERS[tag]["resolution"]
         p = tmp_path / (tag + ".pth")
@@ -203,11 +204,11 @@ def test_setup_attributes_equal_the_references(meta, tmp_path):
         s = _denseclip_setup(cfg, res, None, None)
         m = meta[tag]
         assert m["backbone_type"] == "DenseClip" and m["num_global_tokens"] == 1 and not m["has_blocks"] and m["num_attn_heads"] == 16
-        assert (s["patch_size"], s["embed_dim"]) == (m["patch_size"], m["embed_dim"]) == (16, 512)
-        assert s["cfg"]["model"]["vision"] == m["vision"] and s["cfg"] == cfg and s["cfg"] is not cfg
-        assert 1 + (res // s["patch_size"]) ** 2 == m["num_tokens"] == 1 + m["num_patch_tokens"]
-        assert (s["width"], s["layers"], s["heads"], s["out_dim"], s["resolution"]) == (768, 3, 12, 512, res)
-        assert s["sd"]["pos_embed"].shape == (1, m["num_tokens"], 768)           # used at its own grid: nothing to resample
+        assert (s.patch_size, s.embed_dim) == (m["patch_size"], m["embed_dim"]) == (16, 512)
+        assert s.config["model"]["vision"] == m["vision"] and s.config == cfg and s.config is not cfg
+        assert 1 + (res // s.patch_size) ** 2 == m["num_tokens"] == 1 + m["num_patch_tokens"]
+        assert (s.width, s.depth, s.heads, s.token_dim, s.engine_kw["pretrain_grid"] * s.patch_size) == (768, 3, 12, 512, res)
+        assert s.state_dict["pos_embed"].shape == (1, m["num_tokens"], 768)           # used at its own grid: nothing to resample
     # the reference's .get defaults: 16 and 512 (unreachable past DenseCLIPModel, which indexes the keys: its KeyError)
     cfg = DR.config("r128")
     del cfg["model"]["vision"]["embed_dim"]

@@ -193,28 +193,28 @@ def test_refusals_come_before_the_device_is_touched():
 
 
 def test_setup_attributes_defaults_and_self_only_count(capsys):
-    from patchioner_amd.model import _invite_setup
+    from patchioner_amd.backbones import _invite_setup
     sd16 = W.synth_invite_vit(1, "ViT-B/16", depth=3)
     s = _invite_setup({"name": "ViT-B/16", "checkpoint": sd16, "extract_last_k_th_token": 1}, 224, 224, None)
-    assert (s["patch_size"], s["embed_dim"], s["out_dim"], s["width"], s["heads"], s["layers"], s["resolution"], s["self_only"]) == \
+    assert (s.patch_size, s.embed_dim, s.token_dim, s.width, s.heads, s.depth, s.transform_resolution, s.engine_kw["vit_self_only_layers"]) == \
         (16, 512, 512, 768, 12, 3, 224, 1)
     assert capsys.readouterr().out == ""
     for k, want in ((-1, 0), (0, 0), (2, 2), (3, 3), (7, 3)):           # k <= 0: none; k >= layers: all of them
-        assert _invite_setup({"name": "ViT-B/16", "checkpoint": sd16, "extract_last_k_th_token": k}, 224, 224, None)["self_only"] == want
-    assert _invite_setup({"name": "ViT-B/16", "checkpoint": sd16}, 224, 224, None)["self_only"] == 0        # the default is -1
+        assert _invite_setup({"name": "ViT-B/16", "checkpoint": sd16, "extract_last_k_th_token": k}, 224, 224, None).engine_kw["vit_self_only_layers"] == want
+    assert _invite_setup({"name": "ViT-B/16", "checkpoint": sd16}, 224, 224, None).engine_kw["vit_self_only_layers"] == 0        # the default is -1
     # resolution: the table is resampled to the new grid and the transforms follow the tower
     s = _invite_setup({"name": "ViT-B/16", "checkpoint": sd16, "resolution": 288}, 288, 288, None)
-    assert s["resolution"] == 288 and s["sd"]["pos_embed"].shape == (1, 325, 768)
+    assert s.transform_resolution == 288 and s.state_dict["pos_embed"].shape == (1, 325, 768)
     # an unknown name: the reference's defaults, 32 / 512, each with its printed warning; the B/32 tower agrees with them
     sd32 = {"visual." + k: v for k, v in W.synth_invite_vit(2, "ViT-B/32", depth=1).items()}
     s = _invite_setup({"name": "my-clip", "checkpoint": sd32}, 224, 224, None)
     out = capsys.readouterr().out
     assert "Unknown INViTE model my-clip, using default patch size 32" in out
     assert "Unknown INViTE model my-clip, using default embedding dimension 512" in out
-    assert (s["patch_size"], s["embed_dim"]) == (32, 512)
+    assert (s.patch_size, s.embed_dim) == (32, 512)
     with pytest.raises(ValueError, match="patch_size 32"):              # ... a B/16 tower does not
         _invite_setup({"name": "my-clip", "checkpoint": sd16}, 224, 224, None)
-    assert _invite_setup({"name": "ViT-L/14", "synthetic": 1, "checkpoint": W.synth_invite_vit(3, "ViT-L/14", depth=1)}, 224, 224, None)["embed_dim"] == 768
+    assert _invite_setup({"name": "ViT-L/14", "synthetic": 1, "checkpoint": W.synth_invite_vit(3, "ViT-L/14", depth=1)}, 224, 224, None).embed_dim == 768
     with pytest.raises(RuntimeError, match="not found"):                # synthetic weights need a name of the table
         _invite_setup({"name": "my-clip"}, 224, 224, 5)
 

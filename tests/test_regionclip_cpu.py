@@ -9,7 +9,8 @@ import torch.nn.functional as F
 
 import regionclip_ref as RR
 from patchioner_amd import weights as W
-from patchioner_amd.model import Patchioner, _regionclip_setup
+from patchioner_amd.backbones import _regionclip_setup
+from patchioner_amd.model import Patchioner
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "regionclip.npz")
 LAYERS = (1, 1, 1, 1)
@@ -83,13 +84,13 @@ def test_quirk1_position_table_is_redrawn_from_the_default_generator(capsys):
     a = _regionclip_setup(dict(cfg, checkpoint=W.synth_regionclip_rn(1, "RN50", layers=LAYERS)), "regionclip_resnet50_p32.k", 512, None, None)
     out = capsys.readouterr().out
     assert "Removing incompatible positional embedding" in out and "Checkpoint spatial size: 7x7" in out and "requires 16x16" in out
-    pos = a["sd"]["rn.attnpool.positional_embedding"]
+    pos = a.state_dict["rn.attnpool.positional_embedding"]
     torch.manual_seed(5)
     want = torch.randn(16 * 16 + 1, 2048) / 2048 ** 0.5
     assert torch.equal(pos, want)
     # the native size keeps the checkpoint's table, silently
     b = _regionclip_setup(dict(cfg, MODEL={"RESNETS": {"OUT_FEATURES": ["res5"], "IMAGE_RESOLUTION": 224}}), "regionclip_x", 224, 0, None)
-    assert "Removing" not in capsys.readouterr().out and b["sd"]["rn.attnpool.positional_embedding"].shape == (50, 2048)
+    assert "Removing" not in capsys.readouterr().out and b.state_dict["rn.attnpool.positional_embedding"].shape == (50, 2048)
     with pytest.raises(RuntimeError, match="must match"):       # the table is for IMAGE_RESOLUTION, the crop is another size
         _regionclip_setup(dict(cfg, checkpoint=W.synth_regionclip_rn(1, "RN50", layers=LAYERS)), "regionclip_x", 224, None, None)
 
