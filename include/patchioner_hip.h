@@ -478,6 +478,11 @@ int pio_host_philox_uniform(uint64_t seed, uint32_t row, uint32_t step, float* u
 /* out[n * steps + k] = the uniform of (row0 + n, k) under `seed`, n < N, k < steps: what pio_lm_sample draws for a call whose first row
  * is row `row0` of a larger batch, for callers that split a batch over several calls and pass uniforms_dev. */
 int pio_host_philox_uniforms(uint64_t seed, uint32_t row0, int32_t N, int32_t steps, float* out);
+/* The loader's LayerNorm fold of a linear layer (HOST pointers): W [out][in] (in_major: [in][out], as GPT-2's Conv1D stores it), ln_w / ln_b
+ * [in], bias [out] or NULL -> w [out][in] = W * ln_w, c [out] = row sums of w, d [out] = W ln_b + bias, so that
+ * LN(x) W^T + bias = r (x w^T - mu c) + d.  The decoder kernel tests take their device operands from it. */
+int pio_host_ln_fold(const float* W, int32_t in_major, int64_t in, int64_t out, const float* ln_w, const float* ln_b, const float* bias, float* w,
+                     float* c, float* d);
 
 /* ---- Test hooks: the ViT block kernels one at a time, for the kernel-by-kernel tests.  Caller-owned DEVICE pointers (torch
  *      tensors' data_ptr()), the current HIP device, no pio_handle.  Every size is validated before anything is launched; a refused
@@ -554,6 +559,40 @@ int pio_test_attnpool_in(int32_t operand, const void* x, const float* pos, int32
 /* k_nucleus_sample at any V, without a handle: pio_nucleus_sample's arguments with scores [N, V]. */
 int pio_test_nucleus_sample(const float* scores, int32_t N, int32_t V, float temperature, float top_p, const float* uniforms, int32_t stop_id,
                             int32_t* active, int32_t* tokens, int32_t* kept, pio_stream stream);
+
+/* Decoder kernels (csrc/decoder.hip) one launch at a time, through the layer pass's own dispatch.  E = 768 throughout.
+ * pio_test_dec_workspace: the float count of the split-K workspace and the number of 32-bit ticket words a caller allocates (tickets zeroed). */
+int pio_test_dec_workspace(int64_t* ws_floats, int32_t* ticket_words);
+/* W [n] fp32 (n % 8 == 0, finite) -> the split-fp16 image (out: 4 n bytes) and *unscale (HOST pointer); synchronises the stream */
+int pio_test_dec_split_weights(const float* W, int64_t n, void* out, float* unscale, pio_stream stream);
+enum {
+  PIO_DEC_GEMMS_FAMILY_A = 0,      /* k_dec_gemm, 4 waves x 12 chunks, per 128-row chunk (ragged step, beam step, ragged prefill pass 1) */
+  PIO_DEC_GEMMS_FAMILY_B = 1,      /* k_dec_gemm_b per 128-row chunk (ragged prefill pass 2) */
+  PIO_DEC_GEMMS_BY_ROWS = 2,       /* dec_gemm per 128-row chunk, no split weights (uniform batched prefill) */
+  PIO_DEC_GEMMS_BY_ROWS_SPLIT = 3  /* dec_gemm on all rows, split-fp16 weights from 65 rows when given (uniform step) */
+};
+enum {
+  PIO_DEC_EPI_STORE_LN = 0,        /* out = LN(x) W^T + b             Nout 2304, K 768   (W, bias = d, cvec: the loader's folded operands) */
+  PIO_DEC_EPI_RESID = 1,           /* out += x W^T + b                Nout 768, K 768 or 3072 (3072: split-K, ws and tickets required) */
+  PIO_DEC_EPI_GELU_LN = 2,         /* out = gelu_new(LN(x) W^T + b)   Nout 3072, K 768 */
+  PIO_DEC_EPI_EMBED = 3            /* out = x W^T + b + extra         Nout 768, K 384 / 512 / 640 / 768 / 1024; selector ignored */
+};
+/* X [N][K], W [Nout][K], out [N][Nout], 1 <= N <= 256.  Wsplit (may be NULL): W's split-fp16 image, read by PIO_DEC_GEMMS_BY_ROWS_SPLIT only. */
+int pio_test_dec_gemm(int32_t selector, int32_t epi, const float* W, const void* Wsplit, float unscale, const float* X, int32_t N, int32_t Nout,
+                      int32_t K, const float* bias, const float* cvec, const float* extra, float eps, float* out, float* ws, uint32_t* tickets,
+                      pio_stream stream);
+enum {
+  PIO_DEC_ATTN_STEP = 0,           /* every row at position pos */
+  PIO_DEC_ATTN_PREFILL = 1,        /* rows [n][p], p < P: keys / values of all positions appended, then all positions attended */
+  PIO_DEC_ATTN_RAGGED = 2,         /* row n at position plen[n] + pos */
+  PIO_DEC_ATTN_RAGGED_TAB = 3,     /* ... history key / value j < position read from cache row tab[n * tstride + j] (clamped to [0, N)) */
+  PIO_DEC_ATTN_MASK1 = 4,          /* prefill, appending only for rows with plen[n] <= split */
+  PIO_DEC_ATTN_MASK2 = 5           /* prefill, appending only for rows with plen[n] > split */
+};
+/* qkv [rows][2304], att [rows][768] (rows = N, or N * P in the prefill forms), kcache / vcache [N][max_steps][768]; heads: 768 / heads a
+ * multiple of 32, <= 256; max_steps <= 256.  plen / tab are DEVICE arrays; plen is copied back and checked (the stream is synchronised). */
+int pio_test_dec_attention(int32_t form, const float* qkv, float* kcache, float* vcache, float* att, int32_t N, int32_t heads, int32_t max_steps,
+                           int32_t pos, int32_t P, const int32_t* plen, int32_t split, const int32_t* tab, int32_t tstride, pio_stream stream);
 
 #ifdef __cplusplus
 }

@@ -138,6 +138,7 @@ SIGNATURES = {
     "pio_host_philox4x32": (c_int32, [POINTER(c_uint32), c_uint32, c_uint32, POINTER(c_uint32)]),
     "pio_host_philox_uniform": (c_int32, [c_uint64, c_uint32, c_uint32, POINTER(c_float)]),
     "pio_host_philox_uniforms": (c_int32, [c_uint64, c_uint32, c_int32, c_int32, c_void_p]),
+    "pio_host_ln_fold": (c_int32, [c_void_p, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pio_test_vit_gemm": (c_int32, [c_int32, c_int32, c_int32, POINTER(PioTestGemmArgs), POINTER(c_int32), c_void_p]),
     "pio_test_gemm_route": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     "pio_test_vit_vonly": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(c_int32), c_void_p]),
@@ -152,6 +153,12 @@ SIGNATURES = {
     "pio_test_attnpool_in": (c_int32, [c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "pio_test_nucleus_sample": (c_int32, [c_void_p, c_int32, c_int32, c_float, c_float, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                           c_void_p]),
+    "pio_test_dec_workspace": (c_int32, [POINTER(c_int64), POINTER(c_int32)]),
+    "pio_test_dec_split_weights": (c_int32, [c_void_p, c_int64, c_void_p, POINTER(c_float), c_void_p]),
+    "pio_test_dec_gemm": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                    c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pio_test_dec_attention": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                         c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

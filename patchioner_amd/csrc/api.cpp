@@ -467,11 +467,11 @@ int finalize_vit(pio_context* c) {
   return PIO_OK;
 }
 
-// W [in][out] (Conv1D) or [out][in] (Linear) -> LayerNorm-folded [out][in] weight plus the two epilogue
-// vectors of decoder.hip:  w'_jk = W_jk ln_w_k,  c_j = sum_k w'_jk,  d_j = sum_k ln_b_k W_jk + b_j.
-int upload_ln_folded(pio_context* c, const float* W, bool in_major, int64_t in, int64_t out, const float* lnw,
-                     const float* lnb, const float* bias, float** dw, float** dc, float** dd) {
-  std::vector<float> w((size_t)in * out), cv(out), dv(out);
+// The LayerNorm fold of a linear layer, on the host: W [in][out] (Conv1D, in_major) or [out][in] (Linear) -> the folded [out][in] weight
+// and the two epilogue vectors of decoder.hip:  w'_jk = W_jk ln_w_k in fp32,  c_j = sum_k w'_jk  and  d_j = sum_k ln_b_k W_jk + b_j summed
+// in double and rounded once.  Also exported for the tests as pio_host_ln_fold.
+void ln_fold_host(const float* W, bool in_major, int64_t in, int64_t out, const float* lnw, const float* lnb, const float* bias, float* w,
+                  float* cv, float* dv) {
   for (int64_t j = 0; j < out; ++j) {
     double cs = 0.0, ds = bias ? (double)bias[j] : 0.0;
     for (int64_t k = 0; k < in; ++k) {
@@ -484,6 +484,12 @@ int upload_ln_folded(pio_context* c, const float* W, bool in_major, int64_t in, 
     cv[j] = (float)cs;
     dv[j] = (float)ds;
   }
+}
+// ln_fold_host's three results as device buffers
+int upload_ln_folded(pio_context* c, const float* W, bool in_major, int64_t in, int64_t out, const float* lnw,
+                     const float* lnb, const float* bias, float** dw, float** dc, float** dd) {
+  std::vector<float> w((size_t)in * out), cv(out), dv(out);
+  ln_fold_host(W, in_major, in, out, lnw, lnb, bias, w.data(), cv.data(), dv.data());
   int rc;
   if ((rc = upload_f32(c, w.data(), w.size(), dw))) return rc;
   if ((rc = upload_f32(c, cv.data(), cv.size(), dc))) return rc;
@@ -2179,6 +2185,13 @@ int pio_host_philox_uniforms(uint64_t seed, uint32_t row0, int32_t N, int32_t st
   if (!out || N < 1 || steps < 1) return fail(PIO_ERR_INVALID_ARG, "pio_host_philox_uniforms: bad argument");
   for (int32_t n = 0; n < N; ++n)
     for (int32_t k = 0; k < steps; ++k) out[(size_t)n * steps + k] = philox_uniform(seed, row0 + (uint32_t)n, (uint32_t)k);
+  return PIO_OK;
+}
+
+int pio_host_ln_fold(const float* W, int32_t in_major, int64_t in, int64_t out, const float* ln_w, const float* ln_b, const float* bias, float* w,
+                     float* c, float* d) {
+  if (!W || !ln_w || !ln_b || !w || !c || !d || in < 1 || out < 1) return fail(PIO_ERR_INVALID_ARG, "pio_host_ln_fold: bad argument");
+  ln_fold_host(W, in_major != 0, in, out, ln_w, ln_b, bias, w, c, d);
   return PIO_OK;
 }
 

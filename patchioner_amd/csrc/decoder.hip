@@ -409,7 +409,8 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? PIO_DEC_GEMM_WAVES : 1) void k
 }
 
 // Causal attention for the new position `pos` of prefix n, head h: appends k,v to the cache and attends
-// over positions 0..pos (pos < 128: 30 for DeCap, prompt + 64 for the ViECap head).  One workgroup per (n, head).
+// over positions 0..pos (pos < max_steps <= 256, dec_args_ok: 30 for DeCap, prompt + 64 for the ViECap head; the score array and the
+// four-per-lane soft-max hold 256).  hd = E / heads: any multiple of 32 up to 256.  One workgroup per (n, head).
 //   scores : thread (j = tid>>3, seg = tid&7) takes hd/8 channels of key j -> all key loads of a 32-key
 //            pass are in flight at once; 3 shuffles finish the dot product.
 //   output : thread (c4 = tid % (hd/4), jg = tid / (hd/4)) accumulates 4 channels over keys j = jg (mod NJ);
@@ -970,7 +971,8 @@ __global__ __launch_bounds__(256 * NCG, 1) void k_dec_gemm_s(const u32x4_t* __re
   // row keeps its 22 bits when its largest finite magnitude M is in [2^-10, 2^15) -- every activation a GPT-2 style decoder produces
   // (the residual stream's outlier channels reach a few thousand).  Cheap bookkeeping on the way tells whether that can fail; a workgroup where it can -- a caller may hand in any finite
   // prefix, and the fp32 kernels take it -- stages its slice again, every row with its OWN power of two (M 2^-e in [2^13, 2^14);
-  // inf / NaN elements do not count and make their row NaN, as in the fp32 kernels), undone in the epilogue.  (Per-row scales for
+  // inf / NaN elements do not count and make their row NaN -- the fp32 kernels leave no finite element there either: NaN for a NaN, a mix
+  // of inf and NaN for an inf, whose NaN variance their fmaxf(var, 0) turns into 0), undone in the epilogue.  (Per-row scales for
   // everyone were built first: the second barrier and the conversions waiting behind it cost 2.4 us per kernel; per-chunk maxima in
   // the fast path 1.6 us: three waves share a SIMD, every VALU instruction here is 12 cycles of it.)
   constexpr int XB = NIT % 8 == 0 ? 8 : (NIT % 6 == 0 ? 6 : 4);   // float4 in flight per thread and batch (NIT = 8, 12, 6 or 4)
@@ -2076,17 +2078,23 @@ static hipError_t dec_layers(const DecoderArgs& a, DecGemms g, float* x, float* 
   return hipGetLastError();
 }
 
+// The attention launch of one decode step: N rows of qkv / att, row n at position pos (RAG: plen[n] + pos; tab: history through the table).
+template <bool RAG>
+static void dec_attn_step(const float* qkv, float* kc, float* vc, int E, int heads, int N, int pos, int max_steps, float* att, const int32_t* plen,
+                          const int32_t* tab, int tstride, hipStream_t s) {
+  const dim3 grid(N * heads);
+  if (RAG && tab != nullptr)
+    hipLaunchKernelGGL((k_dec_attention<true, 0, true>), grid, dim3(256), 0, s, qkv, kc, vc, E, heads, pos, max_steps, att, 1, plen, 0, tab, tstride);
+  else
+    hipLaunchKernelGGL(k_dec_attention<RAG>, grid, dim3(256), 0, s, qkv, kc, vc, E, heads, pos, max_steps, att, 1, plen, 0);
+}
+
 // One new position `pos` of every prefix through the transformer layers (x in place; keys / values appended at `pos`).
 // RAG: prefix n's position is plen[n] + pos.  tab (RAG only; batched beam search): the history of row n is read through tab [N][a.max_steps].
 template <bool RAG = false>
 static hipError_t dec_layers_step(const DecoderArgs& a, int pos, hipStream_t s, const int32_t* plen = nullptr, const int32_t* tab = nullptr) {
-  const dim3 grid(a.N * a.heads);
   return dec_layers(a, RAG ? DG_FAMILY_A : DG_BY_ROWS_SPLIT, a.x, a.qkv, a.att, a.hid, a.N, 0, [&](float* kc, float* vc) {
-    if (RAG && tab != nullptr)
-      hipLaunchKernelGGL((k_dec_attention<true, 0, true>), grid, dim3(256), 0, s, a.qkv, kc, vc, a.E, a.heads, pos, a.max_steps, a.att, 1, plen, 0,
-                         tab, a.max_steps);
-    else
-      hipLaunchKernelGGL(k_dec_attention<RAG>, grid, dim3(256), 0, s, a.qkv, kc, vc, a.E, a.heads, pos, a.max_steps, a.att, 1, plen, 0);
+    dec_attn_step<RAG>(a.qkv, kc, vc, a.E, a.heads, a.N, pos, a.max_steps, a.att, plen, tab, a.max_steps, s);
   }, s);
 }
 
@@ -2250,6 +2258,15 @@ __global__ __launch_bounds__(256) void k_dec_last_rows_ragged(const float* __res
   for (int d = threadIdx.x; d < E; d += 256) x[(size_t)n * E + d] = xp[r * E + d];
 }
 
+// The attention of a batched prefill: the keys / values of all P positions of gN prefixes into the cache (MASK: of this pass's prefixes), then
+// every position's attention in one launch (rows [n][p] of qkv / att; a cache row is `ms` positions long).
+template <int MASK>
+static void dec_attn_prefill(const float* qkv, float* kc, float* vc, int E, int heads, int gN, int P, int ms, float* att, const int32_t* pl, int split,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(k_kv_append_masked<MASK>, dim3(gN, P), dim3(192), 0, s, qkv, kc, vc, P, ms, E, pl, split);
+  hipLaunchKernelGGL((k_dec_attention<false, MASK>), dim3(gN * heads, P), dim3(256), 0, s, qkv, kc, vc, E, heads, 0, ms, att, P, pl, split);
+}
+
 // The prompts [N][P][E] of the first N prefixes through the layers: keys / values of the prompt positions into the cache, x[n] = the output
 // of prefix n's last prompt position.  The prefixes go in groups of a.pre_rows / P through the prefill workspace, all their positions as
 // the rows of one layer pass; the GEMMs and MASK follow the table above dec_layers.
@@ -2277,9 +2294,7 @@ static hipError_t dec_prompt_prefill(const DecoderArgs& a, int N, const float* p
     const int32_t* pl = MASK != 0 ? plen + n0 : nullptr;
     hipLaunchKernelGGL(k_dec_prompt_x_all, dim3(gN, P), dim3(256), 0, s, prompt + (size_t)n0 * P * E, a.wpe, P, E, a.pre_x);
     PIO_TRY(dec_layers(a, g, a.pre_x, a.pre_qkv, a.pre_att, a.pre_hid, gN * P, (size_t)n0 * rstride, [&](float* kc, float* vc) {
-      hipLaunchKernelGGL(k_kv_append_masked<MASK>, dim3(gN, P), dim3(192), 0, s, a.pre_qkv, kc, vc, P, ms, E, pl, split);
-      hipLaunchKernelGGL((k_dec_attention<false, MASK>), dim3(gN * a.heads, P), dim3(256), 0, s, a.pre_qkv, kc, vc, E, a.heads, 0, ms, a.pre_att, P,
-                         pl, split);
+      dec_attn_prefill<MASK>(a.pre_qkv, kc, vc, E, a.heads, gN, P, ms, a.pre_att, pl, split, s);
     }, s));
     hipLaunchKernelGGL(k_dec_last_rows_ragged<MASK>, dim3(gN), dim3(256), 0, s, a.pre_x, P, pl, split, E, a.x + (size_t)n0 * E);
   }
@@ -2793,5 +2808,37 @@ hipError_t launch_lm_sample(const DecoderArgs& a, const float* prompt, int P, fl
   }
   return launch_sample_lens(a.ids, N, a.steps, stop_id, lens, s);
 }
+
+// ---- entry points of the kernel-by-kernel tests (test_hooks.cpp; tests/test_gpu_decoder_kernels.py): the launchers above, nothing of their own.
+// One layer GEMM by a line of the table above dec_layers (the (epilogue, LayerNorm) pairs of dec_layers), or the prefix projection.
+hipError_t dec_test_layer_gemm(int selector, int epi, const float* W, const float* X, int rows, int Nout, int K, const float* bias, float* out,
+                               const float* extra, const float* cvec, float eps, float* ws, unsigned* cnt, const void* Wsplit, float unscale,
+                               hipStream_t s) {
+  if (selector < DG_FAMILY_A || selector > DG_BY_ROWS_SPLIT) return hipErrorInvalidValue;
+  const DecGemms g = (DecGemms)selector;
+  switch (epi) {
+    case DE_STORE: return dec_layer_gemm<DE_STORE, 1>(g, W, X, rows, Nout, K, bias, out, cvec, eps, ws, cnt, Wsplit, unscale, s);
+    case DE_RESID: return dec_layer_gemm<DE_RESID, 0>(g, W, X, rows, Nout, K, bias, out, nullptr, 0.f, ws, cnt, Wsplit, unscale, s);
+    case DE_GELU: return dec_layer_gemm<DE_GELU, 1>(g, W, X, rows, Nout, K, bias, out, cvec, eps, ws, cnt, Wsplit, unscale, s);
+    case DE_EMBED: return dec_gemm<DE_EMBED, 0>(W, X, rows, Nout, K, bias, out, extra, nullptr, 0.f, nullptr, nullptr, s);
+  }
+  return hipErrorInvalidValue;
+}
+// One attention launch: form 0 uniform step, 1 uniform prefill, 2 ragged step, 3 ragged step through `tab`, 4 / 5 the masked prefill passes 1 / 2.
+hipError_t dec_test_attention(int form, const float* qkv, float* kc, float* vc, float* att, int E, int heads, int N, int max_steps, int pos, int P,
+                              const int32_t* plen, int split, const int32_t* tab, int tstride, hipStream_t s) {
+  switch (form) {
+    case 0: dec_attn_step<false>(qkv, kc, vc, E, heads, N, pos, max_steps, att, nullptr, nullptr, 0, s); break;
+    case 1: dec_attn_prefill<0>(qkv, kc, vc, E, heads, N, P, max_steps, att, nullptr, 0, s); break;
+    case 2: dec_attn_step<true>(qkv, kc, vc, E, heads, N, pos, max_steps, att, plen, nullptr, 0, s); break;
+    case 3: if (tab == nullptr) return hipErrorInvalidValue;
+            dec_attn_step<true>(qkv, kc, vc, E, heads, N, pos, max_steps, att, plen, tab, tstride, s); break;
+    case 4: dec_attn_prefill<1>(qkv, kc, vc, E, heads, N, P, max_steps, att, plen, split, s); break;
+    case 5: dec_attn_prefill<2>(qkv, kc, vc, E, heads, N, P, max_steps, att, plen, split, s); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+size_t dec_splitk_ws_floats() { return DEC_SPLITK_WS_FLOATS; }
 
 }  // namespace pio

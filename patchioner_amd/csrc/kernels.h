@@ -293,6 +293,15 @@ struct DecoderArgs {
   int pre_rows = 0;
 };
 hipError_t launch_decode_greedy(const DecoderArgs& a, hipStream_t s);
+// The kernel-by-kernel tests' entry points (decoder.hip, end of file; test_hooks.cpp): the layer pass's own GEMM dispatch (selector: a line of the
+// table above dec_layers, 0 family A, 1 family B, 2 by rows, 3 by rows with split-fp16 weights; epi 0 store + LN, 1 residual, 2 GELU + LN, 3 prefix
+// projection) and its attention launches (form 0 step, 1 prefill, 2 ragged step, 3 ragged step through tab, 4 / 5 masked prefill passes).
+hipError_t dec_test_layer_gemm(int selector, int epi, const float* W, const float* X, int rows, int Nout, int K, const float* bias, float* out,
+                               const float* extra, const float* cvec, float eps, float* ws, unsigned* cnt, const void* Wsplit, float unscale,
+                               hipStream_t s);
+hipError_t dec_test_attention(int form, const float* qkv, float* kc, float* vc, float* att, int E, int heads, int N, int max_steps, int pos, int P,
+                              const int32_t* plen, int split, const int32_t* tab, int tstride, hipStream_t s);
+size_t dec_splitk_ws_floats();
 // ViECap greedy search: prompt [N][P][E] at positions 0..P-1, then a.steps greedy tokens (a.pos_base = P - 1)
 hipError_t launch_decode_prompted(const DecoderArgs& a, const float* prompt, int P, hipStream_t s);
 // the same with a prompt length per prefix: prompt [N][Pmax][E] (k_build_prompt_ragged), plen [N] on the device (1 <= plen[n] <= Pmax <= 128,

@@ -1,5 +1,5 @@
-// C ABI test hooks (include/patchioner_hip.h, "Test hooks"): one ViT block kernel per call on caller-owned device buffers, for the
-// kernel-by-kernel tests.  A translation unit of its own: api.cpp's host side (tests/test_asan_host.py) does not link the kernels' launchers.
+// C ABI test hooks (include/patchioner_hip.h, "Test hooks"): one ViT block kernel, or one decoder layer GEMM / attention launch, per call
+// on caller-owned device buffers, for the kernel-by-kernel tests.  A translation unit of its own: api.cpp's host side (tests/test_asan_host.py) does not link the kernels' launchers.
 #include "../../include/patchioner_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -211,6 +211,81 @@ int pio_test_nucleus_sample(const float* scores, int32_t N, int32_t V, float tem
   a.stop_id = stop_id; a.active = active; a.tokens = tokens; a.tok_stride = 1; a.kept = kept;
   const hipError_t e = launch_nucleus_sample(a, (hipStream_t)stream);
   if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_nucleus_sample: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_dec_workspace(int64_t* ws_floats, int32_t* ticket_words) {
+  if (!ws_floats || !ticket_words) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_workspace: null output");
+  *ws_floats = (int64_t)dec_splitk_ws_floats();
+  *ticket_words = DEC_TICKET_WORDS;
+  return PIO_OK;
+}
+
+int pio_test_dec_split_weights(const float* W, int64_t n, void* out, float* unscale, pio_stream stream) {
+  if (!W || !out || !unscale || n < 8 || n % 8 != 0) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_split_weights: W, out, unscale, n a positive multiple of 8");
+  const hipError_t e = dec_split_weights(W, (size_t)n, out, unscale, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_split_weights: weights are not finite");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_dec_split_weights: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_dec_gemm(int32_t selector, int32_t epi, const float* W, const void* Wsplit, float unscale, const float* X, int32_t N, int32_t Nout,
+                      int32_t K, const float* bias, const float* cvec, const float* extra, float eps, float* out, float* ws, uint32_t* tickets,
+                      pio_stream stream) {
+  if (selector < PIO_DEC_GEMMS_FAMILY_A || selector > PIO_DEC_GEMMS_BY_ROWS_SPLIT) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_gemm: selector outside 0..3");
+  if (!W || !X || !bias || !out) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_gemm: null W, X, bias or out");
+  if (N < 1 || N > DEC_MAX_PREFIXES) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_gemm: 1 <= N <= 256");
+  bool ok = false;
+  switch (epi) {
+    case PIO_DEC_EPI_STORE_LN: ok = Nout == 2304 && K == 768 && cvec && eps > 0.f; break;
+    case PIO_DEC_EPI_GELU_LN: ok = Nout == 3072 && K == 768 && cvec && eps > 0.f; break;
+    case PIO_DEC_EPI_RESID: ok = Nout == 768 && (K == 768 || (K == 3072 && ws && tickets)); break;
+    case PIO_DEC_EPI_EMBED: ok = Nout == 768 && (K == 384 || K == 512 || K == 640 || K == 768 || K == 1024) && extra && !Wsplit; break;
+    default: return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_gemm: epi outside 0..3");
+  }
+  if (!ok)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_gemm: epi " + std::to_string(epi) + " refuses Nout " + std::to_string(Nout) + ", K " + std::to_string(K) +
+                                         " (or lacks cvec / eps > 0, extra, or the split-K workspace and tickets)");
+  if (Wsplit && !(unscale > 0.f && std::isfinite(unscale))) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_gemm: Wsplit needs a finite unscale > 0");
+  const bool splitk = K == 3072;     // as in dec_layers: mlp.c_proj, and no other GEMM, gets the workspace
+  const hipError_t e = dec_test_layer_gemm(selector, epi, W, X, N, Nout, K, bias, out, extra, cvec, eps, splitk ? ws : nullptr, splitk ? tickets : nullptr,
+                                           Wsplit, unscale, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_gemm: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_dec_gemm: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_dec_attention(int32_t form, const float* qkv, float* kcache, float* vcache, float* att, int32_t N, int32_t heads, int32_t max_steps,
+                           int32_t pos, int32_t P, const int32_t* plen, int32_t split, const int32_t* tab, int32_t tstride, pio_stream stream) {
+  constexpr int E = 768;
+  if (form < PIO_DEC_ATTN_STEP || form > PIO_DEC_ATTN_MASK2) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: form outside 0..5");
+  if (!qkv || !kcache || !vcache || !att) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: null buffer");
+  if (heads < 1 || E % heads != 0 || (E / heads) % 32 != 0 || E / heads > 256)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: 768 / heads must be a multiple of 32, at most 256");
+  if (N < 1 || N > 4096 || max_steps < 1 || max_steps > 256) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: 1 <= N <= 4096, 1 <= max_steps <= 256");
+  const bool prefill = form == PIO_DEC_ATTN_PREFILL || form == PIO_DEC_ATTN_MASK1 || form == PIO_DEC_ATTN_MASK2;
+  const bool ragged = form == PIO_DEC_ATTN_RAGGED || form == PIO_DEC_ATTN_RAGGED_TAB;
+  if (prefill && (P < 1 || P > max_steps)) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: prefill needs 1 <= P <= max_steps");
+  if (!prefill && (pos < 0 || pos >= max_steps)) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: 0 <= pos < max_steps");
+  if ((ragged || form == PIO_DEC_ATTN_MASK1 || form == PIO_DEC_ATTN_MASK2) && !plen) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: this form needs plen");
+  if (ragged) {
+    std::string lens(sizeof(int32_t) * (size_t)N, '\0');
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemcpy(&lens[0], plen, lens.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_dec_attention: ") + hipGetErrorString(e));
+    int top = 0;
+    for (int n = 0; n < N; ++n) {
+      int32_t v;
+      memcpy(&v, &lens[sizeof(int32_t) * (size_t)n], sizeof(v));
+      if (v < 0 || v + pos >= max_steps) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: 0 <= plen[n], plen[n] + pos < max_steps");
+      top = v + pos > top ? v + pos : top;
+    }
+    if (form == PIO_DEC_ATTN_RAGGED_TAB && (!tab || tstride < top || tstride < 1))
+      return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: the tab form needs tab and tstride >= every row's position");
+  }
+  const hipError_t e = dec_test_attention(form, qkv, kcache, vcache, att, E, heads, N, max_steps, pos, P, plen, split, tab, tstride, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_dec_attention: ") + hipGetErrorString(e));
   return PIO_OK;
 }
 
