@@ -451,6 +451,9 @@ int pio_text_encode(pio_text_handle h, const int32_t* ids_dev, int32_t N, int32_
 int pio_num_tokens(pio_handle h);     /* T */
 int pio_grid_side(pio_handle h);      /* n */
 int64_t pio_bank_rows(pio_handle h);
+/* The form pio_mem_project takes on the loaded bank: 1 split fp16 operands, 0 exact fp32 (the fp32 parity mode, PIO_PROJECT_EXACT, a
+ * non-finite or vanishing max|bank|, or a row whose norm lies below sqrt(dim) 2^-26 max|bank|: the split pair's measured range); -1 no bank. */
+int pio_bank_form(pio_handle h);
 
 /* Host-only (no GPU needed): the load-time position-grid interpolation of pio_finalize_weights
  * (DINOv2 interpolate_pos_encoding: bicubic, antialias, offset 0).  pos [1+grid*grid, dim] -> out [1+n*n, dim]. */
@@ -593,6 +596,26 @@ enum {
  * multiple of 32, <= 256; max_steps <= 256.  plen / tab are DEVICE arrays; plen is copied back and checked (the stream is synchronised). */
 int pio_test_dec_attention(int32_t form, const float* qkv, float* kcache, float* vcache, float* att, int32_t N, int32_t heads, int32_t max_steps,
                            int32_t pos, int32_t P, const int32_t* plen, int32_t split, const int32_t* tab, int32_t tstride, pio_stream stream);
+
+/* Memory-bank projection (csrc/project.hip).
+ * pio_test_project_pass: ONE bank pass -- k_project2 with `groups` query groups of 16 (1, 2, or 3 at D = 768) on `parts` workgroups, then
+ * k_project_combine -- through the function launch_mem_project's loop calls, for the queries q0 .. min(N, q0 + 16 groups) - 1.
+ *   split 0: exact fp32 operands (bank_split / bank_scale unread); 1: split fp16 operands, bank_split [M][2][D] fp16 = pio_test_bank_prep's
+ *   image of bank * bank_scale (a positive finite power of two that brings max|bank| into [2^14, 2^15))
+ *   bank [M][D], inv_norm [M]; q [N][D] UNIT rows (the hook does not normalise); out [N][D]: rows q0 .. of this pass are written
+ *   parts 1 .. 1024: the workgroups launched.  Slabs: units of 16 rows (groups 1) or 32 rows (groups 2, 3), ceil(units / parts) units per
+ *   workgroup, in order; workgroups past the last unit have an empty slab
+ *   part_acc [part_rows][D], part_ml [part_rows][2], part_rows >= parts * 16 groups: workgroup b leaves query n's running maximum m and
+ *   sum l = sum_r e^(z_r - m) at part_ml[b * 16 groups + n], Acc = sum_r e^(z_r - m) bank[r] at part_acc[same row]; an empty slab m = -inf
+ * Refused with PIO_ERR_INVALID_ARG before any launch: another D, groups 3 at D != 768, split without its image and scale, parts outside
+ * 1 .. 1024, part_rows too small, N - q0 < 1, temperature not finite and positive; and split = 1 with one group in a build without the
+ * split instance of the 16-query pass (PIO_PROJECT_SPLIT16 = 0): the hook never runs another form than the one asked for. */
+int pio_test_project_pass(int32_t groups, int32_t split, const float* bank, const void* bank_split, float bank_scale, const float* inv_norm,
+                          int64_t M, int32_t D, const float* q, int32_t N, int32_t q0, float temperature, int32_t parts, float* part_acc,
+                          float* part_ml, int32_t part_rows, float* out, pio_stream stream);
+/* What loading a bank computes, on caller-owned buffers; a NULL output skips its step.  inv_norm [M] = 1 / |bank[r]|; abs_max [1]: the bit
+ * pattern of max |bank| (a non-negative float); bank_split [M][2][D] fp16: hi = fp16(x scale), lo = fp16(x scale - hi). */
+int pio_test_bank_prep(const float* bank, int64_t M, int32_t D, float scale, float* inv_norm, uint32_t* abs_max, void* bank_split, pio_stream stream);
 
 #ifdef __cplusplus
 }

@@ -131,6 +131,7 @@ SIGNATURES = {
     "pio_num_tokens": (c_int32, [c_void_p]),
     "pio_grid_side": (c_int32, [c_void_p]),
     "pio_bank_rows": (c_int64, [c_void_p]),
+    "pio_bank_form": (c_int32, [c_void_p]),
     "pio_host_interpolate_pos_embed": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "pio_host_interpolate_pos_embed_plain": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_double, c_void_p]),
     "pio_host_pil_ksize": (c_int32, [c_int32, c_int32]),
@@ -159,6 +160,9 @@ SIGNATURES = {
                                     c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pio_test_dec_attention": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                          c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "pio_test_project_pass": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32,
+                                        c_float, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "pio_test_bank_prep": (c_int32, [c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

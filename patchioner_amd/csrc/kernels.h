@@ -228,6 +228,11 @@ struct ProjectArgs {
   const void* bank_split; // max|bank| * scale <= 2^15; [M][2][D] fp16, launch_split_bank); 0 / null: the exact fp32 form
 };
 hipError_t launch_mem_project(const ProjectArgs& a, hipStream_t s);
+// one bank pass of launch_mem_project (k_project2 + k_project_combine) for the queries q0 .. q0 + 16 groups - 1 of a.q, which are unit
+// rows already, on `parts` workgroups (1 .. 1024; part_acc / part_ml hold parts * 16 groups rows); a.parts / normalize / n_best unread
+hipError_t launch_project_pass(const ProjectArgs& a, int groups, int q0, int parts, hipStream_t s);
+// whether that pass runs the split-fp16 form on these operands (else exact fp32)
+bool project_pass_is_split(const ProjectArgs& a, int groups);
 // q normalised in place, then top-k cosine similarities and their rows per query (sims_scratch: [16][M] floats)
 hipError_t launch_mem_topk(const float* bank, const float* inv_norm, int64_t M, int D, float* q, int N, int k, float* sims_scratch,
                            float* best_sims, int64_t* best_rows, hipStream_t s);

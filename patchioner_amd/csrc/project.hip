@@ -148,7 +148,11 @@ __global__ __launch_bounds__(256) void k_split_bank(const float* __restrict__ ba
 // (stamps: tools/microbench/project_stamps.hip), so a 32-query pass was bound by its 192 fp32 MFMAs of 32 cycles per tile and SIMD
 // (399 us of 650) plus the soft-max beside them.  An fp16 MFMA does 16x the work per cycle, but T = 0.01 multiplies a cosine's error by
 // 100, so the operands keep 22 significant bits: every factor is split into TWO fp16 values, x S = hi + lo with hi = fp16(x S) and
-// lo = fp16(x S - hi) (S a power of two: lo is a normal fp16 for every |x| >= 2^-17 max|bank|), and the products (Ah + Al)(Bh + Bl)
+// lo = fp16(x S - hi) (S a power of two, max|bank| S in [2^14, 2^15); the hardware keeps fp16 subnormals, in the conversion and in the matrix
+// instruction.  lo is a normal fp16 down to |x| of about 2^-17 max|bank|; below, the pair degrades gracefully -- measured on rows whose
+// largest element is 2^-k max|bank|, T = 0.01: the logit is off by 1.5e-5 down to k = 18, 3.9e-5 at 20, 7.3e-4 at 24, 7.8e-3 at 28, where
+// the pass leaves its error bar; the loader takes the exact form two binades earlier: api.cpp bank_common), and the
+// products (Ah + Al)(Bh + Bl)
 // are fp16 MFMAs with fp32 accumulation: fp16 x fp16 is exact in fp32, what is lost is below 2^-22 of each factor -- against an fp64
 // evaluation the pass is as close as the fp32 form was (2.1e-7 vs 3.9e-7 max on unit-norm outputs, tools/microbench/project_time.py).
 // The BANK IS SPLIT ONCE, when it is loaded (k_split_bank: [row][hi plane D | lo plane D] fp16 of bank * bank_scale, the same 4 D
@@ -437,7 +441,7 @@ __global__ __launch_bounds__(256 * NQG, 1) void k_project2(const float* __restri
       float inv_next[4];
       if (more) {
         const float* ib = inv_norm + (t + 1) * PR_ROWS;
-        const int last = (int)(M - 1 - (t + 1) * PR_ROWS);      // >= 0: tile t+1 starts inside the bank
+        const int last = (int)(M - 1 - (t + 1) * PR_ROWS);      // < 0 where tile t+1 lies wholly past M (second tile of a 32-row unit): ib[last] is inv_norm[M-1]
 #pragma unroll
         for (int i = 0; i < 4; ++i) inv_next[i] = ib[4 * kq + i < last ? 4 * kq + i : last];
       }
@@ -618,9 +622,15 @@ static hipError_t project_pass(const ProjectArgs& a, int q0, int parts, hipStrea
   return hipGetLastError();
 }
 
+// the form a pass of `groups` query groups takes on these operands: split fp16 when the context holds the split image (and, for the
+// 16-query pass, the build carries its split instance), else exact fp32
+bool project_pass_is_split(const ProjectArgs& a, int groups) {
+  return a.bank_scale > 0.f && a.bank_split != nullptr && (groups >= 2 || PIO_PROJECT_SPLIT16);
+}
+
 template <int NQG>
 static hipError_t project_pass_d(const ProjectArgs& a, int q0, int parts, hipStream_t s) {
-  const bool split = a.bank_scale > 0.f && a.bank_split != nullptr && (NQG >= 2 || PIO_PROJECT_SPLIT16);
+  const bool split = project_pass_is_split(a, NQG);
   if constexpr (NQG == 3) {      // 48 queries per pass: the tile's 48 LDS-DMA operations divide among 12 waves only at D = 768
     if (a.D != 768) return hipErrorInvalidValue;
     return split ? project_pass<768, 3, true>(a, q0, parts, s) : project_pass<768, 3, false>(a, q0, parts, s);
@@ -635,6 +645,19 @@ static hipError_t project_pass_d(const ProjectArgs& a, int q0, int parts, hipStr
       default: return hipErrorInvalidValue;
     }
   }
+}
+
+// ONE bank pass: k_project2 with `groups` query groups of 16 on `parts` workgroups, for the queries q0 .. of a.q (unit rows already),
+// then k_project_combine into rows q0 .. of a.out.  Workgroup b leaves its (m, l, Acc) of query n at row b * 16 groups + n of
+// a.part_ml / a.part_acc.  The only place k_project2 is launched from: launch_mem_project's loop and the test hook
+// (pio_test_project_pass) both come through here.
+hipError_t launch_project_pass(const ProjectArgs& a, int groups, int q0, int parts, hipStream_t s) {
+  if (groups < 1 || groups > 3 || parts < 1 || parts > 1024 || q0 < 0 || q0 >= a.N || a.M <= 0) return hipErrorInvalidValue;
+  const int cap = groups * PR_Q, left = a.N - q0, nq = left < cap ? left : cap;
+  const hipError_t e = groups == 3 ? project_pass_d<3>(a, q0, parts, s) : (groups == 2 ? project_pass_d<2>(a, q0, parts, s) : project_pass_d<1>(a, q0, parts, s));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_project_combine, dim3(nq, a.D / 64), dim3(256), 0, s, a.part_acc, a.part_ml, parts, a.D, q0, cap, a.out);
+  return hipGetLastError();
 }
 
 hipError_t launch_mem_project(const ProjectArgs& a, hipStream_t s) {
@@ -652,11 +675,8 @@ hipError_t launch_mem_project(const ProjectArgs& a, hipStream_t s) {
                      a.part_rows >= 3 * PR_Q * (a.parts / 2);
     const int groups = q48 ? 3 : (PIO_PROJECT_Q32 && left > PR_Q ? 2 : 1);
     const int cap = groups * PR_Q, nq = left < cap ? left : cap;
-    const int parts = groups >= 2 ? a.parts / 2 : a.parts;
-    const hipError_t e = groups == 3 ? project_pass_d<3>(a, q0, parts, s) : (groups == 2 ? project_pass_d<2>(a, q0, parts, s) : project_pass_d<1>(a, q0, parts, s));
+    const hipError_t e = launch_project_pass(a, groups, q0, groups >= 2 ? a.parts / 2 : a.parts, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_project_combine, dim3(nq, a.D / 64), dim3(256), 0, s, a.part_acc, a.part_ml, parts, a.D,
-                       q0, cap, a.out);
     q0 += nq;
   }
   if (a.normalize) hipLaunchKernelGGL(k_l2norm_rows, dim3(a.N), dim3(256), 0, s, a.out, a.D);

@@ -1,5 +1,5 @@
-// C ABI test hooks (include/patchioner_hip.h, "Test hooks"): one ViT block kernel, or one decoder layer GEMM / attention launch, per call
-// on caller-owned device buffers, for the kernel-by-kernel tests.  A translation unit of its own: api.cpp's host side (tests/test_asan_host.py) does not link the kernels' launchers.
+// C ABI test hooks (include/patchioner_hip.h, "Test hooks"): one ViT block kernel, one decoder layer GEMM / attention launch, or one bank pass
+// of the memory projection, per call on caller-owned device buffers, for the kernel-by-kernel tests.  A translation unit of its own: api.cpp's host side (tests/test_asan_host.py) does not link the kernels' launchers.
 #include "../../include/patchioner_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -286,6 +286,49 @@ int pio_test_dec_attention(int32_t form, const float* qkv, float* kcache, float*
   const hipError_t e = dec_test_attention(form, qkv, kcache, vcache, att, E, heads, N, max_steps, pos, P, plen, split, tab, tstride, (hipStream_t)stream);
   if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: refused by the launcher");
   if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_dec_attention: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_project_pass(int32_t groups, int32_t split, const float* bank, const void* bank_split, float bank_scale, const float* inv_norm,
+                          int64_t M, int32_t D, const float* q, int32_t N, int32_t q0, float temperature, int32_t parts, float* part_acc,
+                          float* part_ml, int32_t part_rows, float* out, pio_stream stream) {
+  if (!bank || !inv_norm || !q || !part_acc || !part_ml || !out) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: null buffer");
+  if (groups < 1 || groups > 3) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: groups 1, 2 or 3");
+  if (D != 384 && D != 512 && D != 640 && D != 768 && D != 1024) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: D must be 384, 512, 640, 768 or 1024");
+  if (groups == 3 && D != 768) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: the 48-query pass exists at D = 768 only");
+  if (split != 0 && split != 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: split 0 (exact fp32) or 1 (split fp16)");
+  if (split) {
+    int ex = 0;
+    const bool pow2 = std::isfinite(bank_scale) && bank_scale > 0.f && std::frexp(bank_scale, &ex) == 0.5f;
+    if (!bank_split || !pow2) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: the split form needs bank_split and a positive finite power-of-two scale");
+  }
+  if (M < 1 || M > ((int64_t)1 << 40)) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: 1 <= M <= 2^40");
+  if (q0 < 0 || N - q0 < 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: q0 >= 0 and N - q0 >= 1");
+  if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: finite temperature > 0");
+  if (parts < 1 || parts > 1024) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: parts outside 1..1024");
+  if ((int64_t)part_rows < (int64_t)parts * 16 * groups) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: part_acc / part_ml hold fewer than parts * 16 groups rows");
+  ProjectArgs a;
+  memset(&a, 0, sizeof(a));
+  a.bank = bank; a.inv_norm = inv_norm; a.M = M; a.D = D; a.q = const_cast<float*>(q); a.N = N; a.temperature = temperature; a.out = out;
+  a.part_acc = part_acc; a.part_ml = part_ml; a.parts = parts; a.part_rows = part_rows;
+  a.bank_scale = split ? bank_scale : 0.f; a.bank_split = split ? bank_split : nullptr;
+  if ((split != 0) != project_pass_is_split(a, groups))
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: this build has no split instance of the 16-query pass (PIO_PROJECT_SPLIT16 = 0)");
+  const hipError_t e = launch_project_pass(a, groups, q0, parts, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_project_pass: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_project_pass: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_bank_prep(const float* bank, int64_t M, int32_t D, float scale, float* inv_norm, uint32_t* abs_max, void* bank_split, pio_stream stream) {
+  if (!bank || M < 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_bank_prep: bank and M >= 1");
+  if (D != 384 && D != 512 && D != 640 && D != 768 && D != 1024) return fail(PIO_ERR_INVALID_ARG, "pio_test_bank_prep: D must be 384, 512, 640, 768 or 1024");
+  if (bank_split && !(scale > 0.f && std::isfinite(scale))) return fail(PIO_ERR_INVALID_ARG, "pio_test_bank_prep: the split image needs a finite scale > 0");
+  hipError_t e = hipSuccess;
+  if (inv_norm) e = launch_row_inv_norm(bank, M, D, inv_norm, (hipStream_t)stream);
+  if (e == hipSuccess && abs_max) e = launch_abs_max(bank, M * D, abs_max, (hipStream_t)stream);
+  if (e == hipSuccess && bank_split) e = launch_split_bank(bank, M, D, scale, bank_split, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_bank_prep: ") + hipGetErrorString(e));
   return PIO_OK;
 }
 

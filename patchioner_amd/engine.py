@@ -126,6 +126,13 @@ class Engine:
         self.bank_dim = int(bank.shape[1])
         return self.bank_rows
 
+    def bank_form(self) -> str:
+        """"split" (fp16 hi + lo operands) or "exact" (fp32): the form project() takes on the loaded bank (pio_bank_form)."""
+        f = int(self.lib.pio_bank_form(self.h))
+        if f < 0:
+            raise PioError(-3, "memory bank not set")
+        return "split" if f else "exact"
+
     # ------------------------------------------------------------------ measurement
     PROFILE_CLASSES = {"vit_gemm": 0, "vit_attention": 1, "vit_layernorm": 2, "mem_project": 3, "decode": 4}
 
