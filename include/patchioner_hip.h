@@ -597,6 +597,27 @@ enum {
 int pio_test_dec_attention(int32_t form, const float* qkv, float* kcache, float* vcache, float* att, int32_t N, int32_t heads, int32_t max_steps,
                            int32_t pos, int32_t P, const int32_t* plen, int32_t split, const int32_t* tab, int32_t tstride, pio_stream stream);
 
+/* Beam search kernels (csrc/decoder.hip) one launch at a time.
+ * pio_test_beam_select: pio_beam_select (k_beam_select) with V the caller's: lp [W][V] (scores NULL: row 0 only), scores / lens [W] fp32,
+ *   stopped [W] int32 -> out_val [W] fp32, out_idx [W] int64.  1 <= W <= 8, V >= W. */
+int pio_test_beam_select(const float* lp, const float* scores, const float* lens, const int32_t* stopped, int32_t W, int32_t V, float* out_val,
+                         int64_t* out_idx, pio_stream stream);
+/* ONE k_beam_step launch (selection `step` of pio_lm_beam_search and the bookkeeping after it) for N images of W beams, rows r = n W + b,
+ * all state the caller's and updated in place: lp [N W][V] (step 0: its first N rows, one per image), prow [N W] int32 (the prompt length
+ * P_n, on every row of image n), scores / lens [N W] fp32, stopped / tok [N W] int32, hist [N W][steps] int32, tab [N W][tstride] int32,
+ * wte [V][E], wpe [npos][E] -> x [N W][E] = wte[tok] + wpe[min(P_n + step, npos - 1)].  Refused before any launch: W outside 1..8, V < W,
+ * steps outside 1..64, step outside 0..steps - 1, tstride outside 1..256, N outside 1..128, and any row with prow[r] < 1 or
+ * prow[r] + step - 1 >= tstride (prow is copied back: the stream is synchronised). */
+int pio_test_beam_step(const float* lp, int32_t N, int32_t W, int32_t V, int32_t step, int32_t eos0, int32_t eos1, const int32_t* prow, float* scores,
+                       float* lens, int32_t* stopped, int32_t* tok, int32_t* hist, int32_t steps, int32_t* tab, int32_t tstride, const float* wte,
+                       const float* wpe, int32_t npos, int32_t E, float* x, pio_stream stream);
+/* The full-vocabulary head of the beam search and the sampler on caller-owned rows: k_row_stats, then kind 0 k_lm_logits_full (the per-image
+ * path) or 1 k_lm_logits_rows (the batched path), then (log_softmax != 0) k_log_softmax_rows in place.  x [rows][768]; head_w [V][768],
+ * head_c, head_d [V]: pio_host_ln_fold's w, c, d of the tied head (W = wte, LayerNorm ln_f, no bias); stats [rows][2] scratch (mean,
+ * 1 / sqrt(var + eps)); out [rows][V].  1 <= rows <= 256. */
+int pio_test_lm_head_rows(int32_t kind, const float* head_w, const float* head_c, const float* head_d, float eps, const float* x, int32_t rows,
+                          int32_t V, int32_t log_softmax, float* stats, float* out, pio_stream stream);
+
 /* Memory-bank projection (csrc/project.hip).
  * pio_test_project_pass: ONE bank pass -- k_project2 with `groups` query groups of 16 (1, 2, or 3 at D = 768) on `parts` workgroups, then
  * k_project_combine -- through the function launch_mem_project's loop calls, for the queries q0 .. min(N, q0 + 16 groups) - 1.

@@ -160,6 +160,11 @@ SIGNATURES = {
                                     c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pio_test_dec_attention": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                          c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "pio_test_beam_select": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "pio_test_beam_step": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "pio_test_lm_head_rows": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_int32, c_int32, c_void_p,
+                                        c_void_p, c_void_p]),
     "pio_test_project_pass": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32,
                                         c_float, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "pio_test_bank_prep": (c_int32, [c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),

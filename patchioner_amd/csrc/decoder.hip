@@ -2840,5 +2840,23 @@ hipError_t dec_test_attention(int form, const float* qkv, float* kc, float* vc, 
   return hipGetLastError();
 }
 size_t dec_splitk_ws_floats() { return DEC_SPLITK_WS_FLOATS; }
+// One k_beam_step launch for N images on the caller's state (the sizes its shared arrays hold are the hook's to check), and lm_head_rows on
+// the caller's rows and folded head operands.
+hipError_t dec_test_beam_step(const float* lp, int N, int W, int V, int step, int eos0, int eos1, const int32_t* prow, float* scores, float* lens,
+                              int32_t* stopped, int32_t* tok, int32_t* hist, int steps, int32_t* tab, int tstride, const float* wte,
+                              const float* wpe, int npos, int E, float* x, hipStream_t s) {
+  if (N < 1 || W < 1 || W > 8 || V < W || steps < 1 || steps > 64 || step < 0 || step >= steps || tstride < 1 || tstride > 256 || npos < 1 || E < 1)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_beam_step, dim3(N), dim3(1024), 0, s, lp, W, V, step, eos0, eos1, prow, scores, lens, stopped, tok, hist, steps, tab,
+                     tstride, wte, wpe, npos, E, x);
+  return hipGetLastError();
+}
+hipError_t dec_test_lm_head_rows(int kind, const float* head_w, const float* head_c, const float* head_d, float eps, const float* x, int rows,
+                                 int V, bool log_softmax, float* stats, float* out, hipStream_t s) {
+  if ((kind != LOGITS_FULL && kind != LOGITS_ROWS) || rows < 1 || V < 1) return hipErrorInvalidValue;
+  DecoderArgs a{};
+  a.E = 768; a.vocab = V; a.eps = eps; a.head_w = head_w; a.head_c = head_c; a.head_d = head_d; a.x = const_cast<float*>(x);
+  return lm_head_rows(a, rows, (LmLogits)kind, log_softmax, stats, out, s);
+}
 
 }  // namespace pio

@@ -307,6 +307,13 @@ hipError_t dec_test_layer_gemm(int selector, int epi, const float* W, const floa
 hipError_t dec_test_attention(int form, const float* qkv, float* kc, float* vc, float* att, int E, int heads, int N, int max_steps, int pos, int P,
                               const int32_t* plen, int split, const int32_t* tab, int tstride, hipStream_t s);
 size_t dec_splitk_ws_floats();
+// k_beam_step once for N images on caller-owned state, and the full-vocabulary head (lm_head_rows: kind 0 k_lm_logits_full, 1 k_lm_logits_rows;
+// E = 768) on caller-owned rows and folded operands
+hipError_t dec_test_beam_step(const float* lp, int N, int W, int V, int step, int eos0, int eos1, const int32_t* prow, float* scores, float* lens,
+                              int32_t* stopped, int32_t* tok, int32_t* hist, int steps, int32_t* tab, int tstride, const float* wte,
+                              const float* wpe, int npos, int E, float* x, hipStream_t s);
+hipError_t dec_test_lm_head_rows(int kind, const float* head_w, const float* head_c, const float* head_d, float eps, const float* x, int rows,
+                                 int V, bool log_softmax, float* stats, float* out, hipStream_t s);
 // ViECap greedy search: prompt [N][P][E] at positions 0..P-1, then a.steps greedy tokens (a.pos_base = P - 1)
 hipError_t launch_decode_prompted(const DecoderArgs& a, const float* prompt, int P, hipStream_t s);
 // the same with a prompt length per prefix: prompt [N][Pmax][E] (k_build_prompt_ragged), plen [N] on the device (1 <= plen[n] <= Pmax <= 128,

@@ -1,5 +1,5 @@
-// C ABI test hooks (include/patchioner_hip.h, "Test hooks"): one ViT block kernel, one decoder layer GEMM / attention launch, or one bank pass
-// of the memory projection, per call on caller-owned device buffers, for the kernel-by-kernel tests.  A translation unit of its own: api.cpp's host side (tests/test_asan_host.py) does not link the kernels' launchers.
+// C ABI test hooks (include/patchioner_hip.h, "Test hooks"): one ViT block kernel, one decoder layer GEMM / attention launch, one beam
+// selection / bookkeeping step / head pass, or one bank pass of the memory projection, per call on caller-owned device buffers, for the kernel-by-kernel tests.  A translation unit of its own: api.cpp's host side (tests/test_asan_host.py) does not link the kernels' launchers.
 #include "../../include/patchioner_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -286,6 +286,54 @@ int pio_test_dec_attention(int32_t form, const float* qkv, float* kcache, float*
   const hipError_t e = dec_test_attention(form, qkv, kcache, vcache, att, E, heads, N, max_steps, pos, P, plen, split, tab, tstride, (hipStream_t)stream);
   if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_attention: refused by the launcher");
   if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_dec_attention: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_beam_select(const float* lp, const float* scores, const float* lens, const int32_t* stopped, int32_t W, int32_t V, float* out_val,
+                         int64_t* out_idx, pio_stream stream) {
+  if (!lp || !out_val || !out_idx) return fail(PIO_ERR_INVALID_ARG, "pio_test_beam_select: null lp, out_val or out_idx");
+  if (scores && (!lens || !stopped)) return fail(PIO_ERR_INVALID_ARG, "pio_test_beam_select: scores go with lens and stopped");
+  if (W < 1 || W > 8 || V < W) return fail(PIO_ERR_INVALID_ARG, "pio_test_beam_select: 1 <= W <= 8, V >= W");
+  const hipError_t e = launch_beam_select(lp, scores, lens, stopped, W, V, out_val, out_idx, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_beam_select: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_beam_select: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_beam_step(const float* lp, int32_t N, int32_t W, int32_t V, int32_t step, int32_t eos0, int32_t eos1, const int32_t* prow, float* scores,
+                       float* lens, int32_t* stopped, int32_t* tok, int32_t* hist, int32_t steps, int32_t* tab, int32_t tstride, const float* wte,
+                       const float* wpe, int32_t npos, int32_t E, float* x, pio_stream stream) {
+  if (!lp || !prow || !scores || !lens || !stopped || !tok || !hist || !tab || !wte || !wpe || !x)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_beam_step: null buffer");
+  if (N < 1 || N > 128 || W < 1 || W > 8 || V < W) return fail(PIO_ERR_INVALID_ARG, "pio_test_beam_step: 1 <= N <= 128, 1 <= W <= 8, V >= W");
+  if (steps < 1 || steps > 64 || step < 0 || step >= steps) return fail(PIO_ERR_INVALID_ARG, "pio_test_beam_step: 1 <= steps <= 64, 0 <= step < steps");
+  if (tstride < 1 || tstride > 256 || npos < 1 || E < 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_beam_step: 1 <= tstride <= 256, npos >= 1, E >= 1");
+  {
+    std::string rows(sizeof(int32_t) * (size_t)N * W, '\0');
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemcpy(&rows[0], prow, rows.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_beam_step: ") + hipGetErrorString(e));
+    for (int r = 0; r < N * W; ++r) {
+      int32_t P;
+      memcpy(&P, &rows[sizeof(int32_t) * (size_t)r], sizeof(P));
+      if (P < 1 || P + step - 1 >= tstride) return fail(PIO_ERR_INVALID_ARG, "pio_test_beam_step: 1 <= prow[r], prow[r] + step - 1 < tstride");
+    }
+  }
+  const hipError_t e = dec_test_beam_step(lp, N, W, V, step, eos0, eos1, prow, scores, lens, stopped, tok, hist, steps, tab, tstride, wte, wpe, npos,
+                                          E, x, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_beam_step: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_beam_step: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_lm_head_rows(int32_t kind, const float* head_w, const float* head_c, const float* head_d, float eps, const float* x, int32_t rows,
+                          int32_t V, int32_t log_softmax, float* stats, float* out, pio_stream stream) {
+  if (kind != 0 && kind != 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_lm_head_rows: kind 0 (LOGITS_FULL) or 1 (LOGITS_ROWS)");
+  if (!head_w || !head_c || !head_d || !x || !stats || !out) return fail(PIO_ERR_INVALID_ARG, "pio_test_lm_head_rows: null buffer");
+  if (rows < 1 || rows > DEC_MAX_PREFIXES || V < 1 || !(eps > 0.f)) return fail(PIO_ERR_INVALID_ARG, "pio_test_lm_head_rows: 1 <= rows <= 256, V >= 1, eps > 0");
+  const hipError_t e = dec_test_lm_head_rows(kind, head_w, head_c, head_d, eps, x, rows, V, log_softmax != 0, stats, out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_lm_head_rows: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_lm_head_rows: ") + hipGetErrorString(e));
   return PIO_OK;
 }
 
