@@ -265,6 +265,18 @@ int pio_revert_transformation(pio_handle h, const float* x_dev, int32_t N, float
 int pio_decode_greedy(pio_handle h, const float* prefix_dev, int32_t N, int32_t steps, int32_t* ids_dev,
                       float* logprob_dev, pio_stream stream);
 
+/* -- stop_at_eos, DeCap / CapDec: pio_decode_greedy that ends once every row has emitted `eos_id`.  The reference cuts each caption at its
+ *    first end-of-text on the host (P/src/decap/decap.py:173, `.split('<|endoftext|>')[0]`), so nothing a row decodes after it is read.
+ *    The decode runs in segments of `seg` steps (seg >= 1; seg >= steps: one segment), each the launches pio_decode_greedy issues for those
+ *    steps; after a segment the count of rows without a stop goes to pinned host memory, the host waits on an event behind that copy
+ *    (hipEventSynchronize) and launches the next segment only if a row is left.  BLOCKING by nature: for the synchronous paths only.
+ *    ids_dev [N,steps] = canon(ids of pio_decode_greedy): row n up to and including its first eos_id column f_n, then ids[n][f_n] repeated;
+ *    a row without eos_id unchanged -- whatever seg is and whether or not the decode ended early.  No log-probabilities.
+ *    On return *steps_run_host (host memory) = steps the device was given (a multiple of seg, or steps) and all work is enqueued; ids_dev is
+ *    valid once the stream is synchronised.  Checks and capacities as pio_decode_greedy.  Not bracketed by pio_profile_enable. */
+int pio_decode_greedy_stop(pio_handle h, const float* prefix_dev, int32_t N, int32_t steps, int32_t eos_id, int32_t seg, int32_t* ids_dev,
+                           int32_t* steps_run_host, pio_stream stream);
+
 /* ---- ViECap head (P/src/model.py:1394-1398 -> P/src/viecap/entrypoint.py:98-153) -----------------------
  * Weights arrive through pio_load_weight under the checkpoint's own names: `mapping_network.*` (ClipCap.py:122-153) and
  * `gpt.transformer.*` (GPT2LMHeadModel; stored like DeCap's `decoder.transformer.*`).  pio_create: dec_layers = 12,
@@ -292,6 +304,12 @@ int pio_lm_score(pio_handle h, const int32_t* tokens, const int32_t* lens, int32
  * cont == NULL: only_hard_prompt (entrypoint.py:130-131) -- the prompt is the word embeddings of `tokens` alone (Lt >= 1). */
 int pio_viecap_decode(pio_handle h, const float* cont, const int32_t* tokens, int32_t N, int32_t Lt, int32_t soft_first,
                       int32_t steps, int32_t* ids, pio_stream stream);
+/* stop_at_eos, ViECap: pio_viecap_decode that ends once every row has emitted eos0 or eos1 (eos1 < 0: one stop id).  greedy_search cuts a
+ * row at its first full stop (P/src/viecap/search.py:172-190; at one row it returns there, :160-163).  Segments, the hand-over of the live
+ * count, canonical ids [N, steps], *steps_run_host and the blocking nature: as pio_decode_greedy_stop; checks as pio_viecap_decode.  The
+ * segment graphs of up to 8 decode shapes (N, prompt length, steps, seg, stop ids) are kept, each captured as a decode first reaches it. */
+int pio_viecap_decode_stop(pio_handle h, const float* cont, const int32_t* tokens, int32_t N, int32_t Lt, int32_t soft_first, int32_t steps,
+                           int32_t eos0, int32_t eos1, int32_t seg, int32_t* ids, int32_t* steps_run_host, pio_stream stream);
 
 /* The hard prompt on the device (the pipelined head): top_entities + compose_discrete_prompts + tokenisation + pad_sequence.
  * probs [N, K] = pio_viecap_entity_logits' output.  Entities are taken in torch.topk order (descending probability, equal values by the
@@ -637,6 +655,15 @@ int pio_test_project_pass(int32_t groups, int32_t split, const float* bank, cons
 /* What loading a bank computes, on caller-owned buffers; a NULL output skips its step.  inv_norm [M] = 1 / |bank[r]|; abs_max [1]: the bit
  * pattern of max |bank| (a non-negative float); bank_split [M][2][D] fp16: hi = fp16(x scale), lo = fp16(x scale - hi). */
 int pio_test_bank_prep(const float* bank, int64_t M, int32_t D, float scale, float* inv_norm, uint32_t* abs_max, void* bank_split, pio_stream stream);
+
+/* stop_at_eos bookkeeping (dec_stop.hip) on caller-owned device buffers.  ids [N][steps] int32, N <= 256, steps <= 64, 0 <= s0 < s1 <= steps.
+ * scan: first[n] = first column in [s0, s1) of row n that holds stop0 or stop1 (stop1 < 0: none), unless first[n] already names a column
+ *   before s0, which is kept (`steps`: no stop; at s0 == 0 the incoming first[] is ignored); *live = rows without a stop.  Columns outside
+ *   [s0, s1) are not read.
+ * pad: out [N][steps] = ids with every column after first[n] set to ids[n][first[n]] (out != ids). */
+int pio_test_dec_stop_scan(const int32_t* ids, int32_t N, int32_t steps, int32_t s0, int32_t s1, int32_t stop0, int32_t stop1, int32_t* first,
+                           int32_t* live, pio_stream stream);
+int pio_test_dec_stop_pad(const int32_t* ids, const int32_t* first, int32_t N, int32_t steps, int32_t* out, pio_stream stream);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,9 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p]),
     "pio_revert_transformation": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "pio_decode_greedy": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "pio_decode_greedy_stop": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, POINTER(c_int32), c_void_p]),
+    "pio_viecap_decode_stop": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                         POINTER(c_int32), c_void_p]),
     "pio_profile_enable": (c_int32, [c_void_p, c_int32]),
     "pio_profile_read": (c_int32, [c_void_p, c_int32, POINTER(c_double), POINTER(c_int64), POINTER(c_double),
                                    POINTER(c_double)]),
@@ -168,6 +171,8 @@ SIGNATURES = {
     "pio_test_project_pass": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32,
                                         c_float, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "pio_test_bank_prep": (c_int32, [c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pio_test_dec_stop_scan": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "pio_test_dec_stop_pad": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

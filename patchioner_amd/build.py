@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libpatchioner_hip.so")
-SOURCES = ["api.cpp", "vit_gemm.hip", "vit_gemm256.hip", "vit_gemm_roll.hip", "vit_attention.hip", "vit_fp32.hip", "vit_misc.hip", "alpha.hip", "resnet.hip", "region.hip", "project.hip", "decoder.hip", "sample.hip", "viecap.hip", "preprocess.hip", "text_encoder.hip", "text_api.cpp", "resnet_api.cpp", "test_hooks.cpp"]
+SOURCES = ["api.cpp", "vit_gemm.hip", "vit_gemm256.hip", "vit_gemm_roll.hip", "vit_attention.hip", "vit_fp32.hip", "vit_misc.hip", "alpha.hip", "resnet.hip", "region.hip", "project.hip", "decoder.hip", "dec_stop.hip", "sample.hip", "viecap.hip", "preprocess.hip", "text_encoder.hip", "text_api.cpp", "resnet_api.cpp", "test_hooks.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count: the command processor hands the first 16 kernel-argument dwords to the wave in SGPRs instead of the
 # wave fetching them from memory as its first instruction (gfx940+).  Every kernel starts ~0.25 us sooner; the decoder is a chain of

@@ -213,6 +213,24 @@ struct pio_context {
   std::map<PKey, PGraph> pgraphs;
   uint64_t pgraph_clock = 0;
   static constexpr size_t kMaxPGraphs = 12;
+  // stop_at_eos (pio_decode_greedy_stop / pio_viecap_decode_stop): the segment graphs of one decode shape, captured as the decode first reaches
+  // them, and the hand-over of the live-row count.  A cache of their own, sized in whole decodes: a ViECap decode is up to 64 segments
+  // and its prompt length follows every batch, which the 12 entries of pgraphs could not hold; graphs / pgraphs are never touched.
+  enum SKind { STOP_GREEDY, STOP_PROMPTED };
+  struct SKey {
+    SKind kind;
+    int N, P, steps, seg, stop0, stop1;
+    bool operator<(const SKey& o) const {
+      return std::tie(kind, N, P, steps, seg, stop0, stop1) < std::tie(o.kind, o.N, o.P, o.steps, o.seg, o.stop0, o.stop1);
+    }
+  };
+  struct SDecode { std::vector<hipGraphExec_t> segs; uint64_t last_use; hipEvent_t done; };   // segs[k]: steps [k seg, (k + 1) seg), null until captured
+  std::map<SKey, SDecode> sgraphs;
+  static constexpr size_t kMaxSDecodes = 8;
+  int32_t* stop_first = nullptr;                  // [max_prefixes] first stop column per row
+  int32_t* stop_live = nullptr;                   // rows without a stop so far
+  int32_t* stop_live_host = nullptr;              // its pinned host copy
+  hipEvent_t stop_ev = nullptr;                   // recorded behind the copy
   // memory bank
   float* bank = nullptr; float* bank_inv = nullptr; int64_t bank_rows = 0; int bank_dim = 0;
   float bank_scale = 0.f;   // > 0: the projection runs on split fp16 operands of bank * bank_scale (project.hip) ...
@@ -932,6 +950,12 @@ int pio_destroy(pio_handle c) {
   (void)hipDeviceSynchronize();
   for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.second);
   for (auto& g : c->pgraphs) { (void)hipGraphExecDestroy(g.second.exec); if (g.second.done) (void)hipEventDestroy(g.second.done); }
+  for (auto& g : c->sgraphs) {
+    for (hipGraphExec_t e : g.second.segs) if (e) (void)hipGraphExecDestroy(e);
+    if (g.second.done) (void)hipEventDestroy(g.second.done);
+  }
+  if (c->stop_live_host) (void)hipHostFree(c->stop_live_host);
+  if (c->stop_ev) (void)hipEventDestroy(c->stop_ev);
   for (void* p : c->allocs) (void)hipFree(p);
   if (c->rn && PIO_RN_LINKED) rn_destroy(c->rn);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1753,6 +1777,12 @@ hipError_t launch_build_prompt_ragged(const float* cont, const int32_t* tokens, 
 hipError_t launch_decode_prompted_ragged(const DecoderArgs& a, const float* prompt, int Pmax, const int32_t* plen, int split, hipStream_t s)
     __attribute__((weak));
 hipError_t launch_lm_beam_search(const DecoderArgs& a, const BeamArgs& b, hipStream_t s) __attribute__((weak));
+// stop_at_eos: the segment launchers (decoder.hip) and the stop bookkeeping (dec_stop.hip)
+hipError_t launch_decode_greedy_segment(const DecoderArgs& a, int s0, int s1, hipStream_t s) __attribute__((weak));
+hipError_t launch_decode_prompted_segment(const DecoderArgs& a, const float* prompt, int P, int s0, int s1, hipStream_t s) __attribute__((weak));
+hipError_t launch_dec_stop_scan(const int32_t* ids, int N, int steps, int s0, int s1, int stop0, int stop1, int32_t* first, int32_t* live,
+                                hipStream_t s) __attribute__((weak));
+hipError_t launch_dec_stop_pad(const int32_t* ids, const int32_t* first, int N, int steps, int32_t* out, hipStream_t s) __attribute__((weak));
 }  // namespace pio
 }  // extern "C++"
 
@@ -1836,6 +1866,126 @@ int pio_viecap_decode(pio_handle c, const float* cont, const int32_t* tokens, in
   }
   HIP_OK(hipMemcpyAsync(ids, c->ids_buf, (size_t)N * steps * 4, hipMemcpyDeviceToDevice, s));
   return PIO_OK;
+}
+
+// ---- stop_at_eos: a synchronous greedy decode in segments of `seg` steps that ends once every row has emitted a stop id ----
+#define PIO_STOP_LINKED (launch_decode_greedy_segment && launch_decode_prompted_segment && launch_dec_stop_scan && launch_dec_stop_pad)
+
+static int stop_state(pio_context* c) {
+  int rc;
+  if (!c->stop_first) {
+    if ((rc = c->dmalloc(&c->stop_first, (size_t)c->cfg.max_prefixes))) return rc;
+    if ((rc = c->dmalloc(&c->stop_live, 1))) return rc;
+  }
+  if (!c->stop_live_host) HIP_OK(hipHostMalloc((void**)&c->stop_live_host, sizeof(int32_t), 0));
+  if (!c->stop_ev) HIP_OK(hipEventCreateWithFlags(&c->stop_ev, hipEventDisableTiming));
+  return PIO_OK;
+}
+
+// The decode of `key` (its `a`, launched by segment(s0, s1, stream)) until no row is alive: per segment its launches and the scan of its id
+// columns (one graph, captured when the decode first gets there), the live count to pinned memory, an event behind the copy, and the host
+// waits on that event before it decides on the next segment -- no segment is launched ahead of the count, and the last one needs no wait.
+// Then canon(ids) -> ids.  *steps_run = steps the device was given.
+extern "C++" {
+template <class F>
+static int run_stop_decode(pio_context* c, const pio_context::SKey& key, const DecoderArgs& a, F segment, int32_t* ids, int32_t* steps_run,
+                           hipStream_t s) {
+  const int N = key.N, steps = key.steps, seg = key.seg;
+  auto launch = [&](int s0, int s1, hipStream_t cs) -> hipError_t {
+    const hipError_t e = segment(s0, s1, cs);
+    return e != hipSuccess ? e : launch_dec_stop_scan(a.ids, N, steps, s0, s1, key.stop0, key.stop1, c->stop_first, c->stop_live, cs);
+  };
+  pio_context::SDecode* d = nullptr;
+  if (c->use_graph) {
+    auto it = c->sgraphs.find(key);
+    if (it == c->sgraphs.end()) {
+      if (c->sgraphs.size() >= pio_context::kMaxSDecodes) {     // evict the least recently used decode, all its segments (see launch_prompted_graph)
+        auto old = c->sgraphs.begin();
+        for (auto jt = c->sgraphs.begin(); jt != c->sgraphs.end(); ++jt)
+          if (jt->second.last_use < old->second.last_use) old = jt;
+        if (old->second.done) { (void)hipEventSynchronize(old->second.done); (void)hipEventDestroy(old->second.done); }
+        for (hipGraphExec_t e : old->second.segs) if (e) (void)hipGraphExecDestroy(e);
+        c->sgraphs.erase(old);
+      }
+      hipEvent_t done = nullptr;
+      HIP_OK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+      it = c->sgraphs.emplace(key, pio_context::SDecode{std::vector<hipGraphExec_t>((size_t)((steps + seg - 1) / seg), nullptr), 0, done}).first;
+    }
+    d = &it->second;
+    d->last_use = ++c->pgraph_clock;
+  }
+  int run = 0;
+  for (int k = 0, s0 = 0; s0 < steps; ++k, s0 += seg) {
+    const int s1 = s0 + seg < steps ? s0 + seg : steps;
+    if (d) {
+      if (!d->segs[k]) {
+        int rc = capture_exec(c, [&](hipStream_t cs) { return launch(s0, s1, cs); }, "segment decode", &d->segs[k]);
+        if (rc) return rc;
+      }
+      HIP_OK(hipGraphLaunch(d->segs[k], s));
+    } else {
+      HIP_OK(launch(s0, s1, s));
+    }
+    run = s1;
+    if (s1 == steps) break;
+    HIP_OK(hipMemcpyAsync(c->stop_live_host, c->stop_live, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipEventRecord(c->stop_ev, s));
+    HIP_OK(hipEventSynchronize(c->stop_ev));
+    if (*c->stop_live_host <= 0) break;
+  }
+  HIP_OK(launch_dec_stop_pad(a.ids, c->stop_first, N, steps, ids, s));
+  if (d) HIP_OK(hipEventRecord(d->done, s));
+  *steps_run = run;
+  return PIO_OK;
+}
+}  // extern "C++"
+
+int pio_decode_greedy_stop(pio_handle c, const float* prefix, int32_t N, int32_t steps, int32_t eos_id, int32_t seg, int32_t* ids,
+                           int32_t* steps_run_host, pio_stream stream) {
+  if (!c || !prefix || !ids || !steps_run_host) return fail(PIO_ERR_INVALID_ARG, "pio_decode_greedy_stop: null argument");
+  if (!c->has_dec || !c->has_clip_project) return fail(PIO_ERR_NOT_READY, "pio_decode_greedy_stop: decoder weights (with clip_project) not loaded");
+  if (N < 1 || N > c->cfg.max_prefixes) return fail(PIO_ERR_CAPACITY, "pio_decode_greedy_stop: N above max_prefixes");
+  if (steps < 1 || steps > c->cfg.max_steps || steps > 64) return fail(PIO_ERR_CAPACITY, "pio_decode_greedy_stop: steps above max_steps");
+  if (seg < 1 || eos_id < 0) return fail(PIO_ERR_INVALID_ARG, "pio_decode_greedy_stop: seg >= 1 and a stop id >= 0");
+  if (!PIO_STOP_LINKED) return fail(PIO_ERR_NOT_READY, "pio_decode_greedy_stop: built without the kernels");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = stop_state(c))) return rc;
+  const DecoderArgs a = lm_args(c, N, steps, 0, false);
+  HIP_OK(hipMemcpyAsync(c->prefix_buf, prefix, (size_t)N * c->cfg.prefix_size * 4, hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
+  const pio_context::SKey key{pio_context::STOP_GREEDY, N, 0, steps, seg < steps ? seg : steps, eos_id, -1};
+  return run_stop_decode(c, key, a, [&](int s0, int s1, hipStream_t cs) { return launch_decode_greedy_segment(a, s0, s1, cs); }, ids,
+                         steps_run_host, s);
+}
+
+int pio_viecap_decode_stop(pio_handle c, const float* cont, const int32_t* tokens, int32_t N, int32_t Lt, int32_t soft_first, int32_t steps,
+                           int32_t eos0, int32_t eos1, int32_t seg, int32_t* ids, int32_t* steps_run_host, pio_stream stream) {
+  if (!c || !ids || !steps_run_host || (Lt > 0 && !tokens)) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode_stop: null argument");
+  if (!cont && Lt < 1) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode_stop: neither a soft prompt nor prompt tokens");
+  if (!c->has_dec || (cont && !c->has_map)) return fail(PIO_ERR_NOT_READY, "pio_viecap_decode_stop: language model / mapping network not loaded");
+  if (N < 1 || N > c->cfg.max_prefixes) return fail(PIO_ERR_CAPACITY, "pio_viecap_decode_stop: N above max_prefixes");
+  const int Lc = cont ? c->map_Lc : 0;
+  const int P = Lc + Lt;
+  if (Lt < 0 || steps < 1 || steps > 64 || P + steps - 1 > c->cfg.max_steps)
+    return fail(PIO_ERR_CAPACITY, "pio_viecap_decode_stop: prompt + generated positions above max_steps");
+  if (seg < 1 || eos0 < 0) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode_stop: seg >= 1 and a first stop id >= 0 (eos1 < 0: none)");
+  if (!PIO_STOP_LINKED) return fail(PIO_ERR_NOT_READY, "pio_viecap_decode_stop: built without the kernels");
+  HIP_OK(hipSetDevice(c->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  const bool batched_prefill = c->batched_prefill;
+  if ((rc = prompted_workspaces(c, batched_prefill))) return rc;
+  if ((rc = stop_state(c))) return rc;
+  if (Lt > 0) HIP_OK(hipMemcpyAsync(c->tok_buf, tokens, (size_t)N * Lt * 4, hipMemcpyDeviceToDevice, s));
+  HIP_OK(launch_build_prompt(cont, c->tok_buf, c->wte, N, Lc, Lt, c->cfg.dec_embd, c->cfg.dec_vocab, soft_first, c->prompt_buf, s));
+  DecoderArgs a = lm_args(c, N, steps, P - 1);
+  if (batched_prefill) with_prefill(a, c);
+  HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
+  const pio_context::SKey key{pio_context::STOP_PROMPTED, N, P, steps, seg < steps ? seg : steps, eos0, eos1 < 0 ? -1 : eos1};
+  return run_stop_decode(c, key, a, [&](int s0, int s1, hipStream_t cs) { return launch_decode_prompted_segment(a, c->prompt_buf, P, s0, s1, cs); },
+                         ids, steps_run_host, s);
 }
 
 int pio_viecap_compose_prompts(pio_handle c, const float* probs, int32_t N, int32_t K, const int32_t* frag_ids, const int32_t* frag_off,

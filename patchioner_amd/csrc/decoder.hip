@@ -2115,19 +2115,22 @@ static bool dec_args_ok(const DecoderArgs& a, bool filtered, int positions) {
          (a.E / a.heads) <= 256 && a.N <= (filtered ? DEC_MAX_PREFIXES : 64) && ceil_div(a.vocab, 16) <= 4096;
 }
 
-hipError_t launch_decode_greedy(const DecoderArgs& a, hipStream_t s) {
+// The DeCap decode is a prologue (the prefix projection) and steps [0, a.steps); launch_decode_greedy_segment issues a range of them.
+hipError_t launch_decode_greedy_segment(const DecoderArgs& a, int s0, int s1, hipStream_t s) {
   const int N = a.N, E = a.E;
   const bool filtered = PIO_LMHEAD_FILTER && a.logprob == nullptr && a.head_w16 != nullptr;
   // 65..128 prefixes only through the filtered (ids-only) head; the exact head is built for <= 64
-  if (!dec_args_ok(a, filtered, a.steps) || a.pos_base != 0) return hipErrorInvalidValue;
+  if (!dec_args_ok(a, filtered, a.steps) || a.pos_base != 0 || s0 < 0 || s1 <= s0 || s1 > a.steps) return hipErrorInvalidValue;
   // step 0 input: clip_project(prefix) + wpe[0]   (decap.py:124; GPT-2 adds wpe to inputs_embeds)
-  PIO_TRY((dec_gemm<DE_EMBED, 0>(a.clip_w, a.prefix, N, E, a.prefix_size, a.clip_b, a.x, a.wpe, nullptr, 0.f, nullptr, nullptr, s)));
-  for (int step = 0; step < a.steps; ++step) {
+  if (s0 == 0) PIO_TRY((dec_gemm<DE_EMBED, 0>(a.clip_w, a.prefix, N, E, a.prefix_size, a.clip_b, a.x, a.wpe, nullptr, 0.f, nullptr, nullptr, s)));
+  for (int step = s0; step < s1; ++step) {
     PIO_TRY(dec_layers_step(a, step, s));
     PIO_TRY(dec_head_step(a, step, filtered, s));
   }
   return hipGetLastError();
 }
+
+hipError_t launch_decode_greedy(const DecoderArgs& a, hipStream_t s) { return launch_decode_greedy_segment(a, 0, a.steps, s); }
 
 // x[n][:] = prompt[n][pos][:] + wpe[pos][:]
 __global__ __launch_bounds__(256) void k_dec_prompt_x(const float* __restrict__ prompt, const float* __restrict__ wpe, int P, int pos, int E,
@@ -2306,15 +2309,22 @@ static hipError_t dec_prompt_prefill(const DecoderArgs& a, int N, const float* p
 // chosen from the logits of position P-1+k is ids[.][k] and becomes position P+k.  The reference's 64 iterations run
 // the prompt forward plus 64 single-token forwards and never use the logits of the last one: P + steps - 1 positions here.
 // a.pos_base must be P - 1.
-hipError_t launch_decode_prompted(const DecoderArgs& a, const float* prompt, int P, hipStream_t s) {
+// In segments (launch_decode_prompted_segment): the prologue is the prompt prefill, and step k > 0 is the layer pass of position P + k - 1
+// followed by the head, so every segment ends on a head launch and the last step of the decode still has no layer pass behind it.
+hipError_t launch_decode_prompted_segment(const DecoderArgs& a, const float* prompt, int P, int s0, int s1, hipStream_t s) {
   const bool filtered = PIO_LMHEAD_FILTER && a.logprob == nullptr && a.head_w16 != nullptr;
-  if (P < 1 || a.steps < 1 || a.pos_base != P - 1 || !dec_args_ok(a, filtered, P + a.steps - 1)) return hipErrorInvalidValue;
-  PIO_TRY(dec_prompt_prefill<0>(a, a.N, prompt, P, s));
-  for (int step = 0; step < a.steps; ++step) {
+  if (P < 1 || a.steps < 1 || a.pos_base != P - 1 || !dec_args_ok(a, filtered, P + a.steps - 1) || s0 < 0 || s1 <= s0 || s1 > a.steps)
+    return hipErrorInvalidValue;
+  if (s0 == 0) PIO_TRY(dec_prompt_prefill<0>(a, a.N, prompt, P, s));
+  for (int step = s0; step < s1; ++step) {
+    if (step > 0) PIO_TRY(dec_layers_step(a, P + step - 1, s));
     PIO_TRY(dec_head_step(a, step, filtered, s));            // -> ids[.][step], x = wte[id] + wpe[P + step]
-    if (step + 1 < a.steps) PIO_TRY(dec_layers_step(a, P + step, s));
   }
   return hipGetLastError();
+}
+
+hipError_t launch_decode_prompted(const DecoderArgs& a, const float* prompt, int P, hipStream_t s) {
+  return launch_decode_prompted_segment(a, prompt, P, 0, a.steps, s);
 }
 
 // Bits: row n gets the ids pio_viecap_decode gives for that row alone with P = P_n.  That decode runs its prompt through the batched prefill

@@ -321,6 +321,17 @@ hipError_t launch_decode_prompted(const DecoderArgs& a, const float* prompt, int
 // split: prefixes with plen[n] <= split are prefilled on the GEMM family of a one-row-group prefill, the others on the tiled one (16; 256 when
 // the uniform decode would take its prompt position by position) -- row n then has the ids of launch_decode_prompted on that row alone
 hipError_t launch_decode_prompted_ragged(const DecoderArgs& a, const float* prompt, int Pmax, const int32_t* plen, int split, hipStream_t s);
+// stop_at_eos: the two greedy decodes one segment of steps [s0, s1) at a time (0 <= s0 < s1 <= a.steps; a is the FULL decode's, a.steps
+// included: it is the row stride of a.ids).  The segment at s0 == 0 starts with the decode's prologue (DeCap: the prefix projection; ViECap:
+// the prompt prefill); the segments of [0, a.steps) in order issue exactly the launches of launch_decode_greedy / launch_decode_prompted.
+hipError_t launch_decode_greedy_segment(const DecoderArgs& a, int s0, int s1, hipStream_t s);
+hipError_t launch_decode_prompted_segment(const DecoderArgs& a, const float* prompt, int P, int s0, int s1, hipStream_t s);
+// dec_stop.hip: first[n] = first column of ids [N][steps] in [s0, s1) with a stop id (stop1 < 0: one id) unless row n has one before s0
+// (steps: none), *live = rows without one; only columns [s0, s1) are read.  out [N][steps] = ids with every column after first[n] set to
+// ids[n][first[n]] (out != ids).  N <= DEC_MAX_PREFIXES, steps <= 64.
+hipError_t launch_dec_stop_scan(const int32_t* ids, int N, int steps, int s0, int s1, int stop0, int stop1, int32_t* first, int32_t* live,
+                                hipStream_t s);
+hipError_t launch_dec_stop_pad(const int32_t* ids, const int32_t* first, int N, int steps, int32_t* out, hipStream_t s);
 // teacher-forced pass over given tokens [N][Lmax] (rows of lens[n] tokens): nll[n] = sum over p + 1 < lens[n] of -log p(token p+1 | tokens <= p); N <= 64
 hipError_t launch_lm_score(const DecoderArgs& a, const int32_t* tokens, const int32_t* lens, int Lmax, float* nll, hipStream_t s);
 // beam search building blocks (N <= 16 beams per call; stats: [N][2] scratch; logp [N][V] = log softmax of the next-token logits)

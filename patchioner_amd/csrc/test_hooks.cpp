@@ -380,4 +380,22 @@ int pio_test_bank_prep(const float* bank, int64_t M, int32_t D, float scale, flo
   return PIO_OK;
 }
 
+int pio_test_dec_stop_scan(const int32_t* ids, int32_t N, int32_t steps, int32_t s0, int32_t s1, int32_t stop0, int32_t stop1, int32_t* first,
+                           int32_t* live, pio_stream stream) {
+  if (!ids || !first || !live) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_stop_scan: null argument");
+  if (N < 1 || N > DEC_MAX_PREFIXES || steps < 1 || steps > 64 || s0 < 0 || s1 <= s0 || s1 > steps)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_stop_scan: 1 <= N <= 256, 1 <= steps <= 64, 0 <= s0 < s1 <= steps");
+  const hipError_t e = launch_dec_stop_scan(ids, N, steps, s0, s1, stop0, stop1, first, live, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_dec_stop_scan: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_dec_stop_pad(const int32_t* ids, const int32_t* first, int32_t N, int32_t steps, int32_t* out, pio_stream stream) {
+  if (!ids || !first || !out || ids == out) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_stop_pad: null argument, or out == ids");
+  if (N < 1 || N > DEC_MAX_PREFIXES || steps < 1 || steps > 64) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_stop_pad: 1 <= N <= 256, 1 <= steps <= 64");
+  const hipError_t e = launch_dec_stop_pad(ids, first, N, steps, out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_dec_stop_pad: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
 }  // extern "C"

@@ -17,6 +17,28 @@ from . import _lib
 from ._lib import PioConfig, PioError, check, ptr
 
 
+# Steps per segment of a stop_at_eos decode: the segment length with the lowest mean forward() time over the captions-end-by-column-9 and
+# -18 cases of tools/microbench/stop_at_eos_probe.py (1, 2 and 4 lie within 0.06 ms of each other; 8 is 0.5 ms behind).
+DEFAULT_STOP_SEGMENT = 2
+
+
+def _stop_ids(stop_ids, most: int):
+    """None, or [id0, id1] (id1 = -1: one stop id) of 1..``most`` non-negative token ids."""
+    if stop_ids is None:
+        return None
+    ids = [int(i) for i in stop_ids]
+    if not 1 <= len(ids) <= most or min(ids) < 0:
+        raise ValueError("stop ids: 1..%d non-negative token ids (%r)" % (most, stop_ids))
+    return ids + [-1] * (2 - len(ids))
+
+
+def _stop_seg(seg) -> int:
+    seg = DEFAULT_STOP_SEGMENT if seg is None else int(seg)
+    if seg < 1:
+        raise ValueError("the segment of a stop_at_eos decode is >= 1 steps (%r)" % (seg,))
+    return seg
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -60,6 +82,7 @@ class Engine:
         self.prefix_size = prefix_size
         self.max_batch, self.max_prefixes, self.max_steps = max_batch, max_prefixes, max_steps
         self.num_weights = 0
+        self.last_steps_run = None      # steps every chunk of the last stop_at_eos decode ran (decode_greedy / viecap_decode with stop ids)
         self.bank_rows = 0
         self.bank_dim = 0
         self._finalized = False
@@ -504,20 +527,36 @@ class Engine:
             check(self.lib.pio_lm_score(self.h, ptr(tok_d), ptr(lens_d), len(chunk), L, ptr(out[s:s + cap]), _stream()))
         return out
 
-    def viecap_decode(self, cont: Optional[torch.Tensor], tokens: Optional[torch.Tensor], soft_first: bool = True, steps: int = 64) -> torch.Tensor:
+    def viecap_decode(self, cont: Optional[torch.Tensor], tokens: Optional[torch.Tensor], soft_first: bool = True, steps: int = 64,
+                      stop_ids: Optional[Sequence[int]] = None, seg: Optional[int] = None) -> torch.Tensor:
         """cont [N, Lc, E] device (None: only_hard_prompt, the prompt is the tokens' word embeddings alone), tokens [N, Lt] int32
-        (host or device) or None -> greedy ids [N, steps] int32."""
+        (host or device) or None -> greedy ids [N, steps] int32.
+
+        ``stop_ids`` (one or two ids; stop_at_eos): every chunk of max_prefixes rows runs in segments of ``seg`` steps (default
+        DEFAULT_STOP_SEGMENT) and ends once each of its rows has emitted a stop id (pio_viecap_decode_stop: BLOCKING).  The ids are then
+        the canonical table -- a row's first stop id repeated to the end of the row -- and ``last_steps_run`` lists the steps every
+        chunk ran."""
         tok = self._dev(tokens, torch.int32) if tokens is not None else None
         if cont is None and tok is None:
             raise ValueError("viecap_decode: neither a soft prompt nor prompt tokens")
+        stops = _stop_ids(stop_ids, 2)
         N = cont.shape[0] if cont is not None else tok.shape[0]
         Lt = int(tok.shape[1]) if tok is not None else 0
         ids = torch.empty(N, steps, device=self.device, dtype=torch.int32)
+        ran = []
         for s in range(0, N, self.max_prefixes):
             e = min(N, s + self.max_prefixes)
-            check(self.lib.pio_viecap_decode(self.h, ptr(cont[s:e].contiguous()) if cont is not None else None,
-                                             ptr(tok[s:e].contiguous()) if tok is not None else None,
-                                             e - s, Lt, 1 if soft_first else 0, int(steps), ptr(ids[s:e]), _stream()))
+            c = ptr(cont[s:e].contiguous()) if cont is not None else None
+            t = ptr(tok[s:e].contiguous()) if tok is not None else None
+            if stops is None:
+                check(self.lib.pio_viecap_decode(self.h, c, t, e - s, Lt, 1 if soft_first else 0, int(steps), ptr(ids[s:e]), _stream()))
+                continue
+            n = ctypes.c_int32(0)
+            check(self.lib.pio_viecap_decode_stop(self.h, c, t, e - s, Lt, 1 if soft_first else 0, int(steps), stops[0], stops[1],
+                                                  _stop_seg(seg), ptr(ids[s:e]), ctypes.byref(n), _stream()))
+            ran.append(int(n.value))
+        if stops is not None:
+            self.last_steps_run = ran
         return ids
 
     def viecap_compose_prompts(self, probs: torch.Tensor, frag, top_k: int, threshold: float, pad_id: int,
@@ -702,18 +741,36 @@ class Engine:
         return ids, lens
 
     # ------------------------------------------------------------------ a11/a12 decoder
-    def decode_greedy(self, prefix: torch.Tensor, steps: int = 30, want_logprob: bool = False):
+    def decode_greedy(self, prefix: torch.Tensor, steps: int = 30, want_logprob: bool = False, stop_id: Optional[int] = None,
+                      seg: Optional[int] = None):
+        """prefix [N, prefix_size] -> (greedy ids [N, steps] int32, per-token log-probabilities [N, steps] or None).
+
+        ``stop_id`` (stop_at_eos; no log-probabilities): every chunk of max_prefixes rows runs in segments of ``seg`` steps (default
+        DEFAULT_STOP_SEGMENT) and ends once each of its rows has emitted ``stop_id`` (pio_decode_greedy_stop: BLOCKING).  The ids are then
+        the canonical table -- a row's first stop id repeated to the end of the row -- and ``last_steps_run`` lists the steps every chunk
+        ran."""
+        if stop_id is not None and want_logprob:
+            raise ValueError("decode_greedy: a decode that stops early has no log-probabilities (the score sums all of them)")
+        stops = _stop_ids(None if stop_id is None else [stop_id], 1)
         prefix = self._dev(prefix)
         N = prefix.shape[0]
         ids = torch.empty(N, steps, device=self.device, dtype=torch.int32)
         lp = torch.empty(N, steps, device=self.device, dtype=torch.float32) if want_logprob else None
         chunk = min(self.max_prefixes, 64) if want_logprob else self.max_prefixes     # the exact (log-prob) head: <= 64 rows
+        ran = []
         for s in range(0, N, chunk):
             e = min(N, s + chunk)
-            check(self.lib.pio_decode_greedy(self.h, ptr(prefix[s:e]), e - s, steps, ptr(ids[s:e]),
-                                             ptr(lp[s:e]) if want_logprob else None, _stream()))
+            if stops is None:
+                check(self.lib.pio_decode_greedy(self.h, ptr(prefix[s:e]), e - s, steps, ptr(ids[s:e]),
+                                                 ptr(lp[s:e]) if want_logprob else None, _stream()))
+                continue
+            n = ctypes.c_int32(0)
+            check(self.lib.pio_decode_greedy_stop(self.h, ptr(prefix[s:e]), e - s, steps, stops[0], _stop_seg(seg), ptr(ids[s:e]),
+                                                  ctypes.byref(n), _stream()))
+            ran.append(int(n.value))
+        if stops is not None:
+            self.last_steps_run = ran
         return ids, lp
-
 
 
 class DecoderClone:

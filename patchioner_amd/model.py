@@ -15,6 +15,10 @@ Build-specific config keys (there is no network on the target, so nothing is fet
   memory_bank      path (.npy / .pt / .h5) or tensor [M, D] of the text memory bank
   synthetic_seed   int: synthesise any weights / bank not given (seeded; see weights.py)
   max_batch, max_prefixes, vit_dtype ("fp16" | "bf16")
+  stop_at_eos      False (default) | True: the synchronous greedy decodes (DeCap / CapDec without compute_scores, the greedy ViECap head)
+                   end once every caption of the call has emitted its end token, in segments of stop_segment steps (None: the engine's
+                   default, engine.DEFAULT_STOP_SEGMENT).  Same strings; forward_async and the pipelines run full length as before.
+                   ``model.stop_at_eos`` may be toggled after construction
   denseclip_config   a dict of the DenseCLIP YAML's structure, a .yaml path, or a config name (denseclip.py); denseclip_config_dir: where
                    names are looked up (else $PIO_DENSECLIP_CONFIG_DIR, else the two built-in names); denseclip_checkpoint: a local
                    checkpoint file or {'state_dict': ...} that replaces the config's checkpoint.path
@@ -88,7 +92,7 @@ class Patchioner(nn.Module):
                  dino_weights=None, memory_bank=None, synthetic_seed=None, max_batch=16, max_prefixes=128,
                  vit_dtype="fp16", memory_bank_texts=None, clip_text_weights=None, clip_text_dtype="fp16",
                  talk2dino_projection_weights=None, denseclip_config_dir=None, denseclip_checkpoint=None, sparse_last_block=None,
-                 **kwargs):
+                 stop_at_eos=False, stop_segment=None, **kwargs):
         super().__init__(**kwargs)
         given = dict(proxyclip_clipmodel=proxyclip_clipmodel)
         for k in _OUT_OF_SCOPE:
@@ -260,6 +264,11 @@ class Patchioner(nn.Module):
             self.text_dataset = [t if isinstance(t, bytes) else str(t).encode("utf-8") for t in self.text_dataset]
         self.tokenizer = ClipDetokenizer()
         self.last_ids = None
+        # stop_at_eos: see the module docstring; last_decode_steps: steps every chunk of the last caption_tokens decode ran when it went
+        # through the stopping entry points, None after a full-length or deferred decode
+        self.stop_at_eos = bool(stop_at_eos)
+        self.stop_segment = None if stop_segment is None else int(stop_segment)
+        self.last_decode_steps = None
         self.call_log = None            # tests: a list collects (decoder prefix, greedy ids) of every caption_tokens call
         self._defer = False
         self.dino = self.engine     # callers test `model.dino is not None`
@@ -343,6 +352,8 @@ class Patchioner(nn.Module):
             denseclip_config_dir=config.get('denseclip_config_dir', None),
             denseclip_checkpoint=config.get('denseclip_checkpoint', None),
             sparse_last_block=config.get('sparse_last_block', None),
+            stop_at_eos=config.get('stop_at_eos', False),
+            stop_segment=config.get('stop_segment', None),
         )
         model.to(device)
         return model
@@ -781,6 +792,7 @@ class Patchioner(nn.Module):
     def caption_tokens(self, dino_tokens, project=True, return_n_best_sims=None, compute_scores: bool = False):
         """P/src/model.py:1392-1423."""
         eng = self.engine
+        self.last_decode_steps = None
         if self.viecap is not None:
             if return_n_best_sims:
                 raise Exception("return_n_best_sims is not supported with viecap")
@@ -796,8 +808,9 @@ class Patchioner(nn.Module):
                 ids = self.viecap.enqueue(dino_tokens)
                 self.last_ids = ids
                 return _PendingVieCapCaptions(ids, self.viecap)
-            out = self.viecap.forward(dino_tokens, compute_scores=compute_scores)
+            out = self.viecap.forward(dino_tokens, compute_scores=compute_scores, stop_at_eos=self.stop_at_eos, stop_segment=self.stop_segment)
             self.last_ids = self.viecap.last_ids      # [N, 64] ids of the greedy search: what dist.sharded_* gathers
+            self.last_decode_steps = self.viecap.last_decode_steps
             return out
         if self.clipcap is not None:
             if return_n_best_sims:
@@ -839,7 +852,12 @@ class Patchioner(nn.Module):
             prefix = xd
         if self.embed_inversion:
             prefix = eng.revert_transformation(prefix)
-        ids, lp = eng.decode_greedy(prefix, steps=30, want_logprob=compute_scores)
+        if self.stop_at_eos and not self._defer and not compute_scores:
+            # the score is exp of the sum of all 30 log-probabilities, so compute_scores takes the full decode
+            ids, lp = eng.decode_greedy(prefix, steps=30, stop_id=self.tokenizer.eot_id, seg=self.stop_segment)
+            self.last_decode_steps = list(eng.last_steps_run)
+        else:
+            ids, lp = eng.decode_greedy(prefix, steps=30, want_logprob=compute_scores)
         self.last_ids = ids
         if self.call_log is not None:
             self.call_log.append((prefix.detach().clone(), ids.detach().clone()))

@@ -26,6 +26,7 @@ class ClipDetokenizer:
         offs, blob = z["offsets"], z["blob"].tobytes()
         self.table = [blob[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
         self.vocab_size = len(self.table)
+        self.eot_id = self.vocab_size - 1          # <|endoftext|>, 49407: the id batch_captions' cut stands for (stop_at_eos stops on it)
 
     def decode(self, tokens: Sequence[int]) -> str:
         """Raises (IndexError) for ids outside the vocabulary, like the reference's KeyError."""

@@ -425,8 +425,14 @@ class VieCapHead:
             out.append(self.tokenizer.decode(list(row_ids[b][:int(row_lens[b])])))
         return out
 
-    def forward(self, image_features: torch.Tensor, compute_scores: bool = False):
-        """entrypoint.py:98-153.  image_features [N, clip_hidden_size] is L2-normalised IN PLACE (line 108)."""
+    def forward(self, image_features: torch.Tensor, compute_scores: bool = False, stop_at_eos: bool = False, stop_segment: Optional[int] = None):
+        """entrypoint.py:98-153.  image_features [N, clip_hidden_size] is L2-normalised IN PLACE (line 108).
+
+        ``stop_at_eos`` (greedy search only; the beam search runs as it does without it): the decode ends once every row has emitted an
+        end-of-sentence id (Engine.viecap_decode with ``stop_ids``), in segments of ``stop_segment`` steps.  The captions -- and the
+        perplexities, which are recomputed from them -- are those of the full decode; ``last_ids`` is the canonical id table and
+        ``last_decode_steps`` the steps every chunk ran (None after a full-length decode)."""
+        self.last_decode_steps = None
         a, eng = self.args, self.engine
         pad_id = self.tokenizer.pad_token_id if self.tokenizer.pad_token_id is not None else 0
         x = image_features
@@ -460,7 +466,11 @@ class VieCapHead:
             if compute_scores:
                 return out, self.compute_perplexity(out)
             return out
-        ids = eng.viecap_decode(cont, tokens, soft_first=soft_first, steps=64)
+        if stop_at_eos:
+            ids = eng.viecap_decode(cont, tokens, soft_first=soft_first, steps=64, stop_ids=self.eos, seg=stop_segment)
+            self.last_decode_steps = list(eng.last_steps_run)
+        else:
+            ids = eng.viecap_decode(cont, tokens, soft_first=soft_first, steps=64)
         self.last_ids = ids
         out = self.captions(ids.cpu().tolist())
         if compute_scores:
