@@ -665,6 +665,43 @@ int pio_test_dec_stop_scan(const int32_t* ids, int32_t N, int32_t steps, int32_t
                            int32_t* live, pio_stream stream);
 int pio_test_dec_stop_pad(const int32_t* ids, const int32_t* first, int32_t N, int32_t steps, int32_t* out, pio_stream stream);
 
+/* The exact-fp32 kernels, one launch per call, all pointers DEVICE fp32 unless said otherwise; no call synchronises.
+ * pio_test_sgemm (k_sgemm_tn): C [M][ldc] = alpha * A [M][lda] . W [N][ldw]^T (+ bias [N], may be NULL) (relu) (resid: + the old C).
+ *   Columns n >= N of C and rows m >= M are never written.  A and W 16-byte aligned; lda, ldw >= K; ldc >= N.  The launcher refuses K < 32,
+ *   K % 32 != 0, lda % 4 != 0, ldw % 4 != 0 and relu with resid: PIO_ERR_INVALID_ARG, nothing launched. */
+int pio_test_sgemm(const float* A, int32_t lda, const float* W, int32_t ldw, const float* bias, float alpha, float* C, int32_t ldc, int32_t M,
+                   int32_t N, int32_t K, int32_t relu, int32_t resid, pio_stream stream);
+/* qkv [B*Tp][3D] (q | k | v along a row, head h in columns [64 h, 64 h + 64) of each third), D == 64 H -> out [B*Tp][D].
+ * kind 0 (k_attention_f32): sequence b attends its first len keys, len = lens[b] (DEVICE [B] int32, the caller keeps 0 <= lens[b] <= Tp;
+ *   not read back) or T without lens; rows len <= t < Tp are written as zero.  kind 1 (k_text_attention_f32): causal, query t attends
+ *   keys 0 .. t; takes no lens, T ignored. */
+int pio_test_attention_f32(int32_t kind, const float* qkv, int32_t B, int32_t H, int32_t T, int32_t Tp, int32_t D, float scale,
+                           const int32_t* lens, float* out, pio_stream stream);
+/* k_layernorm_f32: y [M][D] = LayerNorm(x [M][D]) * w + b (biased variance, eps under the root); y == x is allowed (the CLIP pre-norm) */
+int pio_test_layernorm_f32(const float* x, const float* w, const float* b, float eps, int32_t M, int32_t D, float* y, pio_stream stream);
+enum {
+  PIO_POINTWISE_GELU_ERF = 0,      /* y = 0.5 y (1 + erf(y / sqrt 2))      k_gelu_f32 act 0 */
+  PIO_POINTWISE_QUICKGELU = 1,     /* y = y / (1 + exp(-1.702 y))          k_gelu_f32 act 1 */
+  PIO_POINTWISE_TANH = 2,          /* y = tanh(y)                          k_activation_f32 act 2 */
+  PIO_POINTWISE_SIGMOID = 3,       /* y = 1 / (1 + exp(-y))                k_activation_f32 act 3 */
+  PIO_POINTWISE_RESID_LS = 4       /* y[i] += aux[i] * ls[i % D]           k_resid_ls_f32 (aux [n], ls [D]; ops 0..3 ignore aux, ls, D) */
+};
+/* in place on y [n], 1 <= n <= 2^31 */
+int pio_test_pointwise_f32(int32_t op, float* y, int64_t n, const float* aux, const float* ls, int32_t D, pio_stream stream);
+/* k_im2col_f32: imgs [B][3][S][S] -> out [B (S/p)^2][Kpad], column c p^2 + py p + px; the columns >= 3 p^2 are NOT written (the forward
+ * zero-fills its buffer once, at creation) */
+int pio_test_im2col_f32(const float* imgs, int32_t B, int32_t S, int32_t p, int32_t Kpad, float* out, pio_stream stream);
+/* k_embed_scatter_f32: x [B*Tp][D] rows b Tp + G + i = emb [B*n2][D] row b n2 + i + pos [1 + n2][D] row 1 + i; other rows not written */
+int pio_test_embed_scatter_f32(const float* emb, const float* pos, int32_t B, int32_t n2, int32_t Tp, int32_t G, int32_t D, float* x,
+                               pio_stream stream);
+/* k_text_embed: ids [N][L] int32 -> x [N*Tp][W] = tok [V][W] row id + pos [>= L][W] row t; rows t >= L zero.  An id outside [0, V) gives a
+ * zero row and ORs 1 into *err (DEVICE int32, zeroed by the caller).  Tp >= L, Tp % 8 == 0. */
+int pio_test_text_embed(const int32_t* ids, int32_t N, int32_t L, int32_t Tp, int32_t V, int32_t W, const float* tok, const float* pos, float* x,
+                        int32_t* err, pio_stream stream);
+/* k_text_pool: out [N][E] = LayerNorm(x [N*Tp][W] row s Tp + (first arg-max of ids [N][L] row s); lw, lb [W], eps) . proj [W][E]; W <= 1024 */
+int pio_test_text_pool(const float* x, const int32_t* ids, int32_t N, int32_t L, int32_t Tp, int32_t W, int32_t E, const float* lw,
+                       const float* lb, float eps, const float* proj, float* out, pio_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,18 @@ SIGNATURES = {
     "pio_test_bank_prep": (c_int32, [c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pio_test_dec_stop_scan": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "pio_test_dec_stop_pad": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "pio_test_sgemm": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_float, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                 c_int32, c_int32, c_void_p]),
+    "pio_test_attention_f32": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                                         c_void_p]),
+    "pio_test_layernorm_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p]),
+    "pio_test_pointwise_f32": (c_int32, [c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
+    "pio_test_im2col_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "pio_test_embed_scatter_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "pio_test_text_embed": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+    "pio_test_text_pool": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_float,
+                                     c_void_p, c_void_p, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -1,10 +1,12 @@
 // C ABI test hooks (include/patchioner_hip.h, "Test hooks"): one ViT block kernel, one decoder layer GEMM / attention launch, one beam
-// selection / bookkeeping step / head pass, or one bank pass of the memory projection, per call on caller-owned device buffers, for the kernel-by-kernel tests.  A translation unit of its own: api.cpp's host side (tests/test_asan_host.py) does not link the kernels' launchers.
+// selection / bookkeeping step / head pass, one bank pass of the memory projection, or one exact-fp32 kernel (GEMM, attention, LayerNorm,
+// pointwise, im2col / scatter, text embed / pool), per call on caller-owned device buffers, for the kernel-by-kernel tests.  A translation unit of its own: api.cpp's host side (tests/test_asan_host.py) does not link the kernels' launchers.
 #include "../../include/patchioner_hip.h"
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <string>
 
@@ -395,6 +397,102 @@ int pio_test_dec_stop_pad(const int32_t* ids, const int32_t* first, int32_t N, i
   if (N < 1 || N > DEC_MAX_PREFIXES || steps < 1 || steps > 64) return fail(PIO_ERR_INVALID_ARG, "pio_test_dec_stop_pad: 1 <= N <= 256, 1 <= steps <= 64");
   const hipError_t e = launch_dec_stop_pad(ids, first, N, steps, out, (hipStream_t)stream);
   if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_dec_stop_pad: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+// ---- the exact-fp32 kernels (viecap.hip k_sgemm_tn / k_layernorm_f32 / k_activation_f32, vit_fp32.hip, text_encoder.hip's fp32 side)
+int pio_test_sgemm(const float* A, int32_t lda, const float* W, int32_t ldw, const float* bias, float alpha, float* C, int32_t ldc, int32_t M,
+                   int32_t N, int32_t K, int32_t relu, int32_t resid, pio_stream stream) {
+  if (!A || !W || !C) return fail(PIO_ERR_INVALID_ARG, "pio_test_sgemm: null A, W or C");
+  if (((uintptr_t)A | (uintptr_t)W) % 16 != 0) return fail(PIO_ERR_INVALID_ARG, "pio_test_sgemm: A and W must be 16-byte aligned");
+  if (M < 1 || N < 1 || K < 1 || lda < K || ldw < K || ldc < N) return fail(PIO_ERR_INVALID_ARG, "pio_test_sgemm: M, N, K >= 1, lda >= K, ldw >= K, ldc >= N");
+  if (!std::isfinite(alpha)) return fail(PIO_ERR_INVALID_ARG, "pio_test_sgemm: finite alpha");
+  const hipError_t e = launch_sgemm_tn(A, lda, W, ldw, bias, alpha, C, ldc, M, N, K, relu, resid, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_sgemm: refused by the launcher (K >= 32, K % 32 == 0, lda % 4 == 0, ldw % 4 == 0, not relu with resid): K " +
+                                         std::to_string(K) + ", lda " + std::to_string(lda) + ", ldw " + std::to_string(ldw) + ", relu " +
+                                         std::to_string(relu) + ", resid " + std::to_string(resid));
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_sgemm: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_attention_f32(int32_t kind, const float* qkv, int32_t B, int32_t H, int32_t T, int32_t Tp, int32_t D, float scale,
+                           const int32_t* lens, float* out, pio_stream stream) {
+  if (kind != 0 && kind != 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_attention_f32: kind 0 (ViT) or 1 (text, causal)");
+  if (!qkv || !out || qkv == out) return fail(PIO_ERR_INVALID_ARG, "pio_test_attention_f32: null buffer, or out == qkv");
+  if (B < 1 || H < 1 || D != 64 * H || Tp < 1 || Tp > 4096 || (int64_t)B * H > 65535 || !(scale > 0.f) || !std::isfinite(scale))
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_attention_f32: B, H >= 1, B H <= 65535, D == 64 H, 1 <= Tp <= 4096, finite scale > 0");
+  if (kind == 0 && (T < 1 || T > Tp)) return fail(PIO_ERR_INVALID_ARG, "pio_test_attention_f32: ViT attention needs 1 <= T <= Tp");
+  if (kind == 1 && lens) return fail(PIO_ERR_INVALID_ARG, "pio_test_attention_f32: text attention takes no lens");
+  const hipError_t e = kind == 0 ? launch_attention_f32(qkv, B, H, T, Tp, D, scale, lens, out, (hipStream_t)stream)
+                                 : launch_text_attention_f32(qkv, B, H, Tp, D, scale, out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_attention_f32: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_attention_f32: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_layernorm_f32(const float* x, const float* w, const float* b, float eps, int32_t M, int32_t D, float* y, pio_stream stream) {
+  if (!x || !w || !b || !y) return fail(PIO_ERR_INVALID_ARG, "pio_test_layernorm_f32: null x, w, b or y");
+  if (M < 1 || D < 1 || !(eps > 0.f)) return fail(PIO_ERR_INVALID_ARG, "pio_test_layernorm_f32: M >= 1, D >= 1, eps > 0");
+  const hipError_t e = launch_layernorm_f32(x, w, b, eps, M, D, y, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_layernorm_f32: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_pointwise_f32(int32_t op, float* y, int64_t n, const float* aux, const float* ls, int32_t D, pio_stream stream) {
+  if (op < PIO_POINTWISE_GELU_ERF || op > PIO_POINTWISE_RESID_LS) return fail(PIO_ERR_INVALID_ARG, "pio_test_pointwise_f32: op outside 0..4");
+  if (!y || n < 1 || n > ((int64_t)1 << 31)) return fail(PIO_ERR_INVALID_ARG, "pio_test_pointwise_f32: y and 1 <= n <= 2^31");
+  hipError_t e;
+  if (op == PIO_POINTWISE_RESID_LS) {
+    if (!aux || !ls || aux == y || D < 1) return fail(PIO_ERR_INVALID_ARG, "pio_test_pointwise_f32: resid_ls needs aux != y, ls and D >= 1");
+    e = launch_resid_ls_f32(y, aux, ls, (size_t)n, D, (hipStream_t)stream);
+  } else if (op == PIO_POINTWISE_TANH || op == PIO_POINTWISE_SIGMOID) {
+    e = launch_activation_f32(y, (size_t)n, op, (hipStream_t)stream);
+  } else {
+    e = launch_gelu_f32(y, (size_t)n, op, (hipStream_t)stream);
+  }
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_pointwise_f32: refused by the launcher");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_pointwise_f32: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_im2col_f32(const float* imgs, int32_t B, int32_t S, int32_t p, int32_t Kpad, float* out, pio_stream stream) {
+  if (!imgs || !out || B < 1 || p < 1 || S < p || S % p != 0 || Kpad < 3 * p * p)
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_im2col_f32: imgs, out, B >= 1, S a multiple of p, Kpad >= 3 p^2");
+  if ((int64_t)B * 3 * S * S > ((int64_t)1 << 30) || (int64_t)B * (S / p) * (S / p) * Kpad > ((int64_t)1 << 30))
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_im2col_f32: at most 2^30 input and 2^30 output elements");
+  const hipError_t e = launch_im2col_f32(imgs, B, S, p, S / p, Kpad, out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_im2col_f32: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_embed_scatter_f32(const float* emb, const float* pos, int32_t B, int32_t n2, int32_t Tp, int32_t G, int32_t D, float* x,
+                               pio_stream stream) {
+  if (!emb || !pos || !x) return fail(PIO_ERR_INVALID_ARG, "pio_test_embed_scatter_f32: null emb, pos or x");
+  if (B < 1 || n2 < 1 || G < 0 || Tp < G + n2 || D < 1 || (int64_t)B * Tp * D > ((int64_t)1 << 30))
+    return fail(PIO_ERR_INVALID_ARG, "pio_test_embed_scatter_f32: B, n2, D >= 1, G >= 0, Tp >= G + n2, B Tp D <= 2^30");
+  const hipError_t e = launch_embed_scatter_f32(emb, pos, B, n2, Tp, G, D, x, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_embed_scatter_f32: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_text_embed(const int32_t* ids, int32_t N, int32_t L, int32_t Tp, int32_t V, int32_t W, const float* tok, const float* pos, float* x,
+                        int32_t* err, pio_stream stream) {
+  if (!ids || !tok || !pos || !x || !err) return fail(PIO_ERR_INVALID_ARG, "pio_test_text_embed: null ids, tok, pos, x or err");
+  if (V < 1 || W < 1 || N < 1 || (int64_t)N * Tp > ((int64_t)1 << 24)) return fail(PIO_ERR_INVALID_ARG, "pio_test_text_embed: N, V, W >= 1, N Tp <= 2^24");
+  const hipError_t e = launch_text_embed(ids, N, L, Tp, V, W, tok, pos, x, err, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_text_embed: refused by the launcher (N, L >= 1, Tp >= L, Tp % 8 == 0)");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_text_embed: ") + hipGetErrorString(e));
+  return PIO_OK;
+}
+
+int pio_test_text_pool(const float* x, const int32_t* ids, int32_t N, int32_t L, int32_t Tp, int32_t W, int32_t E, const float* lw,
+                       const float* lb, float eps, const float* proj, float* out, pio_stream stream) {
+  if (!x || !ids || !lw || !lb || !proj || !out) return fail(PIO_ERR_INVALID_ARG, "pio_test_text_pool: null buffer");
+  if (W < 1 || E < 1 || !(eps > 0.f)) return fail(PIO_ERR_INVALID_ARG, "pio_test_text_pool: W >= 1, E >= 1, eps > 0");
+  const hipError_t e = launch_text_pool(x, ids, N, L, Tp, W, E, lw, lb, eps, proj, out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(PIO_ERR_INVALID_ARG, "pio_test_text_pool: refused by the launcher (N, L >= 1, W <= 1024, Tp >= L)");
+  if (e != hipSuccess) return fail(PIO_ERR_HIP, std::string("pio_test_text_pool: ") + hipGetErrorString(e));
   return PIO_OK;
 }
 
