@@ -79,51 +79,119 @@ struct VitLayerDev {
   const void* vw; const float* vb;
 };
 
-struct GraphKey {
-  int N, steps, lp;
-  bool operator<(const GraphKey& o) const {
-    if (N != o.N) return N < o.N;
-    if (steps != o.steps) return steps < o.steps;
-    return lp < o.lp;
+// launch(stream) captured on `cs` (the handle's capture stream) and instantiated -> *exec: the only place that begins and ends a capture.
+// what: the decode's name in the error message.
+template <class F>
+int capture_exec(hipStream_t cs, F launch, const char* what, hipGraphExec_t* exec) {
+  hipGraph_t graph = nullptr;
+  HIP_OK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+  hipError_t le = launch(cs);
+  hipError_t ce = hipStreamEndCapture(cs, &graph);
+  if (le != hipSuccess) {
+    if (graph) (void)hipGraphDestroy(graph);
+    return fail(PIO_ERR_HIP, std::string(what) + " capture: " + hipGetErrorString(le));
+  }
+  HIP_OK(ce);
+  const hipError_t ie = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  HIP_OK(ie);
+  return PIO_OK;
+}
+
+// ---- the decode graphs: one key, one entry, one cache ----
+// Which decode a cached graph holds, and every launch parameter that is baked into its kernel arguments: the shape (N, P, steps) and the
+// parameters of its kind.  P of a RAGGED / BEAM graph is the upper bound Pmax; the lengths themselves are read from the device.
+enum DecodeKind { GREEDY, PROMPTED, RAGGED, BEAM, SAMPLE, STOP_GREEDY, STOP_PROMPTED };
+struct DecodeKey {
+  DecodeKind kind;
+  int N, P, steps;
+  int lp = 0;                                                  // GREEDY: whether log-probabilities are written
+  int W = 0, has_plen = 0, eos0 = 0, eos1 = 0;                 // BEAM: beam width, whether prompt lengths were given, end-of-sentence ids
+  int stop_id = 0; uint32_t temp_bits = 0, top_p_bits = 0;     // SAMPLE: stop token, the bits of temperature and top_p
+  int seg = 0, stop0 = 0, stop1 = 0;                           // STOP_*: steps per segment graph, the stop ids (stop1 -1: none)
+  bool operator<(const DecodeKey& o) const {
+    return std::tie(kind, N, P, steps, lp, W, has_plen, eos0, eos1, stop_id, temp_bits, top_p_bits, seg, stop0, stop1) <
+           std::tie(o.kind, o.N, o.P, o.steps, o.lp, o.W, o.has_plen, o.eos0, o.eos1, o.stop_id, o.temp_bits, o.top_p_bits, o.seg, o.stop0, o.stop1);
   }
 };
+// The graphs of one decode.  A single-graph decode holds one exec; a stop decode one per segment, execs[k] = steps [k seg, (k + 1) seg), null
+// until the decode first gets there (or after a capture that failed: the next use captures it).
+// done: recorded behind the decode's last launch, so that eviction can wait for it after the caller's stream has gone (an event outlives the
+// stream it was recorded on; a stored stream handle does not).  Null in a cache that never evicts.
+struct GraphEntry {
+  std::vector<hipGraphExec_t> execs;
+  uint64_t last_use = 0;
+  hipEvent_t done = nullptr;
+};
+// A handle's graphs of some decode kinds: at most `capacity` decodes, the least recently used one evicted (0: unbounded).
+struct GraphCache {
+  explicit GraphCache(size_t cap) : capacity(cap) {}
+
+  // *out = the entry of `key`, created with `n_execs` null execs if the cache has none.  use_graph false (PIO_NO_GRAPH=1): *out = null,
+  // which graph_launch takes as "launch eagerly".
+  int get(bool use_graph, const DecodeKey& key, size_t n_execs, GraphEntry** out) {
+    *out = nullptr;
+    if (!use_graph) return PIO_OK;
+    auto it = entries.find(key);
+    if (it == entries.end()) {
+      hipEvent_t done = nullptr;
+      if (capacity > 0) HIP_OK(hipEventCreateWithFlags(&done, hipEventDisableTiming));     // before anything is evicted: a failure leaves the cache as it was
+      if (capacity > 0 && entries.size() >= capacity) {
+        auto old = entries.begin();
+        for (auto jt = entries.begin(); jt != entries.end(); ++jt)
+          if (jt->second.last_use < old->second.last_use) old = jt;
+        // it may still be running where it was last launched: wait for the event recorded behind that launch.  Whatever the wait says, the entry goes.
+        drop(old->second);
+        entries.erase(old);
+      }
+      GraphEntry e;
+      e.execs.assign(n_execs, nullptr);
+      e.done = done;
+      it = entries.emplace(key, std::move(e)).first;
+    }
+    it->second.last_use = ++clock;
+    *out = &it->second;
+    return PIO_OK;
+  }
+  void clear() {
+    for (auto& kv : entries) drop(kv.second);
+    entries.clear();
+  }
+
+ private:
+  static void drop(GraphEntry& e) {
+    if (e.done) { (void)hipEventSynchronize(e.done); (void)hipEventDestroy(e.done); }
+    for (hipGraphExec_t x : e.execs) if (x) (void)hipGraphExecDestroy(x);
+  }
+  size_t capacity;
+  std::map<DecodeKey, GraphEntry> entries;
+  uint64_t clock = 0;
+};
+
+// Exec k of `e`, captured from launch(cs) if it is still null; nothing to do for a null entry.
+template <class F>
+int graph_capture(hipStream_t cs, GraphEntry* e, size_t k, F launch, const char* what) {
+  return (e && !e->execs[k]) ? capture_exec(cs, launch, what, &e->execs[k]) : PIO_OK;
+}
+// The one graph / eager fork: exec k of `e` on `s`, or for a null entry (PIO_NO_GRAPH=1) the launches themselves.
+template <class F>
+hipError_t graph_or_eager(const GraphEntry* e, size_t k, F launch, hipStream_t s) {
+  return e ? hipGraphLaunch(e->execs[k], s) : launch(s);
+}
+template <class F>
+int graph_launch(hipStream_t cs, GraphEntry* e, size_t k, F launch, const char* what, hipStream_t s) {
+  const int rc = graph_capture(cs, e, k, launch, what);
+  if (rc) return rc;
+  HIP_OK(graph_or_eager(e, k, launch, s));
+  return PIO_OK;
+}
+// behind the last launch of a decode whose cache evicts
+int graph_done(GraphEntry* e, hipStream_t s) {
+  if (e && e->done) HIP_OK(hipEventRecord(e->done, s));
+  return PIO_OK;
+}
 
 }  // namespace
-
-// alpha.hip's launchers.  The library references them strongly: without alpha.hip its load fails (build() loads it with every
-// symbol bound).  Only the host-only AddressSanitizer build of this file alone (tests/hipstub, whose stub launchers predate these)
-// references them weakly; there the AlphaCLIP entry points report PIO_ERR_NOT_READY.
-#if defined(__SANITIZE_ADDRESS__)
-#define PIO_ALPHA_HOST_ONLY 1
-#elif defined(__has_feature)
-#if __has_feature(address_sanitizer)
-#define PIO_ALPHA_HOST_ONLY 1
-#endif
-#endif
-#ifdef PIO_ALPHA_HOST_ONLY
-namespace pio {
-hipError_t launch_im2col_alpha(int, const float*, const int32_t*, const uint8_t*, int, int, int, int, int, void*, hipStream_t) __attribute__((weak));
-hipError_t launch_region_masks(const float*, const int32_t*, const double*, const int32_t*, int, int, float, uint8_t*, hipStream_t) __attribute__((weak));
-}  // namespace pio
-#define PIO_ALPHA_LINKED (&launch_im2col_alpha != nullptr && &launch_region_masks != nullptr)
-// the sparse last block's two launchers, likewise younger than the stub: pio_vit_forward_rows / pio_region_reduce_rows report
-// PIO_ERR_NOT_READY there
-namespace pio {
-hipError_t launch_gather_rows(const float*, const int32_t*, int, int, int, int, int, float*, int32_t*, hipStream_t) __attribute__((weak));
-hipError_t launch_region_reduce_rows(const float*, const int32_t*, int, int, const float*, const int32_t*, int, float, float*, hipStream_t) __attribute__((weak));
-}  // namespace pio
-#define PIO_ROWS_LINKED (&launch_gather_rows != nullptr && &launch_region_reduce_rows != nullptr)
-namespace pio {
-int rn_build(const pio_config&, const RnGet&, RnNet**) __attribute__((weak));
-void rn_destroy(RnNet*) __attribute__((weak));
-int rn_forward(RnNet*, const float*, int, float*, hipStream_t) __attribute__((weak));
-}  // namespace pio
-#define PIO_RN_LINKED (&rn_build != nullptr && &rn_destroy != nullptr && &rn_forward != nullptr)
-#else
-#define PIO_ALPHA_LINKED true
-#define PIO_ROWS_LINKED true
-#define PIO_RN_LINKED true
-#endif
 
 struct pio_context {
   pio_config cfg;
@@ -169,7 +237,14 @@ struct pio_context {
         *vcache = nullptr, *logits = nullptr, *splitk_ws = nullptr, *prefix_buf = nullptr, *logprob_buf = nullptr;
   int32_t* ids_buf = nullptr;
   unsigned* splitk_cnt = nullptr;
-  std::map<GraphKey, hipGraphExec_t> graphs;
+  // The decode graphs, captured on capture_stream at first use and destroyed by pio_destroy (GraphCache::clear).  Three budgets, so that
+  // no kind of decode evicts another's graphs:
+  //   greedy   pio_decode_greedy: (N, steps, logprob) only, a handful of keys per run, never evicted
+  //   prompted pio_viecap_decode / _ragged, pio_lm_beam_search, pio_lm_sample: the prompt length follows the hard prompt of every batch, so
+  //            a long run meets many keys and a graph is ~ (P + steps) x 60 kernel nodes: 12 graphs
+  //   stop     the two *_stop entry points, sized in whole decodes: a ViECap decode is up to 64 segment graphs and its prompt length follows
+  //            every batch, which 12 single graphs could not hold: 8 decodes
+  GraphCache greedy_graphs{0}, prompted_graphs{12}, stop_graphs{8};
   hipStream_t capture_stream = nullptr;
   bool use_graph = true;
   bool lm_tail = false;                           // <= 16 prefixes: the arg-max filter as the ticketed tail of the LM head kernel (PIO_LM_TAIL=1 at pio_create; measured slower, decoder.hip)
@@ -194,39 +269,7 @@ struct pio_context {
   static constexpr int kPrefillRows = 2048;
   int32_t* tok_buf = nullptr;                     // [max_prefixes][max_steps]
   int32_t* plen_buf = nullptr;                    // [max_prefixes] prompt length per row of a ragged decode (pio_viecap_decode_ragged)
-  // Which decode a cached graph holds, and every launch parameter that is baked into its kernel arguments: the shape (N, P, steps) and the
-  // parameters of its kind.  P of a RAGGED / BEAM graph is the upper bound Pmax; the lengths themselves are read from the device.
-  enum PKind { PROMPTED, RAGGED, BEAM, SAMPLE };
-  struct PKey {
-    PKind kind;
-    int N, P, steps;
-    int W = 0, has_plen = 0, eos0 = 0, eos1 = 0;                 // BEAM: beam width, whether prompt lengths were given, end-of-sentence ids
-    int stop_id = 0; uint32_t temp_bits = 0, top_p_bits = 0;     // SAMPLE: stop token, the bits of temperature and top_p
-    bool operator<(const PKey& o) const {
-      return std::tie(kind, N, P, steps, W, has_plen, eos0, eos1, stop_id, temp_bits, top_p_bits) <
-             std::tie(o.kind, o.N, o.P, o.steps, o.W, o.has_plen, o.eos0, o.eos1, o.stop_id, o.temp_bits, o.top_p_bits);
-    }
-  };
-  // prompted-decode graphs, keyed by (rows, prompt positions, steps).  The prompt length follows the hard prompt of every batch,
-  // so a long run meets many keys: the cache is a small LRU (a graph is ~ (P + steps) x 60 kernel nodes) and evicted execs are destroyed.
-  struct PGraph { hipGraphExec_t exec; uint64_t last_use; hipEvent_t done; };     // done: recorded behind the graph's last launch (valid after the caller's stream has gone)
-  std::map<PKey, PGraph> pgraphs;
-  uint64_t pgraph_clock = 0;
-  static constexpr size_t kMaxPGraphs = 12;
-  // stop_at_eos (pio_decode_greedy_stop / pio_viecap_decode_stop): the segment graphs of one decode shape, captured as the decode first reaches
-  // them, and the hand-over of the live-row count.  A cache of their own, sized in whole decodes: a ViECap decode is up to 64 segments
-  // and its prompt length follows every batch, which the 12 entries of pgraphs could not hold; graphs / pgraphs are never touched.
-  enum SKind { STOP_GREEDY, STOP_PROMPTED };
-  struct SKey {
-    SKind kind;
-    int N, P, steps, seg, stop0, stop1;
-    bool operator<(const SKey& o) const {
-      return std::tie(kind, N, P, steps, seg, stop0, stop1) < std::tie(o.kind, o.N, o.P, o.steps, o.seg, o.stop0, o.stop1);
-    }
-  };
-  struct SDecode { std::vector<hipGraphExec_t> segs; uint64_t last_use; hipEvent_t done; };   // segs[k]: steps [k seg, (k + 1) seg), null until captured
-  std::map<SKey, SDecode> sgraphs;
-  static constexpr size_t kMaxSDecodes = 8;
+  // stop_at_eos: the hand-over of the live-row count between the segments of a decode (stop_state)
   int32_t* stop_first = nullptr;                  // [max_prefixes] first stop column per row
   int32_t* stop_live = nullptr;                   // rows without a stop so far
   int32_t* stop_live_host = nullptr;              // its pinned host copy
@@ -948,16 +991,13 @@ int pio_destroy(pio_handle c) {
   if (c->parent) c->parent->clones -= 1;
   (void)hipSetDevice(c->cfg.device);
   (void)hipDeviceSynchronize();
-  for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.second);
-  for (auto& g : c->pgraphs) { (void)hipGraphExecDestroy(g.second.exec); if (g.second.done) (void)hipEventDestroy(g.second.done); }
-  for (auto& g : c->sgraphs) {
-    for (hipGraphExec_t e : g.second.segs) if (e) (void)hipGraphExecDestroy(e);
-    if (g.second.done) (void)hipEventDestroy(g.second.done);
-  }
+  c->greedy_graphs.clear();
+  c->prompted_graphs.clear();
+  c->stop_graphs.clear();
   if (c->stop_live_host) (void)hipHostFree(c->stop_live_host);
   if (c->stop_ev) (void)hipEventDestroy(c->stop_ev);
   for (void* p : c->allocs) (void)hipFree(p);
-  if (c->rn && PIO_RN_LINKED) rn_destroy(c->rn);
+  if (c->rn) rn_destroy(c->rn);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   for (auto& sl : c->prep_slots) {
     if (sl.host) (void)hipHostFree(sl.host);
@@ -994,7 +1034,6 @@ int pio_finalize_weights(pio_handle c) {
   int rc;
   if (c->cfg.vit_arch == 3 && find(c, "rn.conv1.weight")) {
     // RegionCLIP's ResNet tower: resnet_api.cpp packs it, every key through need()'s shape check
-    if (!PIO_RN_LINKED) return fail(PIO_ERR_NOT_READY, "pio_finalize_weights: the ResNet tower is not linked");
     const RnGet get = [c](const std::string& key, int64_t numel, const float** data) {
       const HostTensor* t;
       const int r = need(c, key, {numel}, &t);
@@ -1251,7 +1290,6 @@ static int vit_forward_impl(pio_handle c, const float* imgs, int32_t B, const in
                             float* qkv_last, hipStream_t s, const RowSel* rows = nullptr) {
   const int D = c->D, M = B * c->Tp;
   const bool alpha = c->cfg.vit_arch == 2;
-  if (alpha && !PIO_ALPHA_LINKED) return fail(PIO_ERR_NOT_READY, "vit forward: the alpha-channel kernels are not linked");
   if (c->vit_f32) {
     if (alpha)
       HIP_OK(launch_im2col_alpha(2, imgs, img_of_region, masks, B, c->cfg.crop_dim, c->cfg.patch_size, c->n, c->Kpad, c->f_ape, s));
@@ -1338,7 +1376,6 @@ int pio_vit_forward_rows(pio_handle c, const float* imgs, int32_t B, const int32
   if (!c->has_vit) return fail(PIO_ERR_NOT_READY, "pio_vit_forward_rows: backbone weights not loaded");
   if (c->cfg.vit_arch > 1 || c->cfg.vit_self_only_layers != 0 || c->vit_f32 || !c->xs)
     return fail(PIO_ERR_INVALID_ARG, "pio_vit_forward_rows: the fp16 / bf16 DINOv2 ViT and the CLIP ViT without self-only blocks only (call pio_vit_forward)");
-  if (!PIO_ROWS_LINKED) return fail(PIO_ERR_NOT_READY, "pio_vit_forward_rows: the row-selection kernels are not linked");
   if (B < 1 || B > c->cfg.max_batch) return fail(PIO_ERR_CAPACITY, "pio_vit_forward_rows: batch above max_batch");
   RowSel r;
   if (!quads_valid(quads_host, img_off_host, B, c->Tp, &r.max_per_img))
@@ -1373,7 +1410,6 @@ int pio_region_reduce_rows(pio_handle c, const float* tokens, const int32_t* row
                            int32_t R, float scale, float* out, pio_stream stream) {
   if (!c || !tokens || !row_map || !weights || !out) return fail(PIO_ERR_INVALID_ARG, "pio_region_reduce_rows: null argument");
   if (R < 1) return fail(PIO_ERR_INVALID_ARG, "pio_region_reduce_rows: empty input");
-  if (!PIO_ROWS_LINKED) return fail(PIO_ERR_NOT_READY, "pio_region_reduce_rows: the row-selection kernels are not linked");
   REGION_GRID_OK(c, "pio_region_reduce_rows");
   HIP_OK(hipSetDevice(c->cfg.device));
   HIP_OK(launch_region_reduce_rows(tokens, row_map, c->Dout, c->n2, weights, img_index, R, scale, out, (hipStream_t)stream));
@@ -1402,7 +1438,6 @@ int pio_region_masks(pio_handle c, const float* boxes, const int32_t* box_off, c
                      int32_t grid, float divisor, uint8_t* masks, pio_stream stream) {
   if (!c || !box_off || !pt_off || !masks) return fail(PIO_ERR_INVALID_ARG, "pio_region_masks: null argument");
   if (R < 1 || grid < 1 || grid > 4096 || !(divisor > 0.f)) return fail(PIO_ERR_INVALID_ARG, "pio_region_masks: R >= 1, 1 <= grid <= 4096, divisor > 0");
-  if (!PIO_ALPHA_LINKED) return fail(PIO_ERR_NOT_READY, "pio_region_masks: the alpha-channel kernels are not linked");
   HIP_OK(hipSetDevice(c->cfg.device));
   HIP_OK(launch_region_masks(boxes, box_off, pts, pt_off, R, grid, divisor, masks, (hipStream_t)stream));
   return PIO_OK;
@@ -1587,39 +1622,31 @@ static void with_prefill(DecoderArgs& a, const pio_context* c) {
   a.pre_x = c->pre_x; a.pre_qkv = c->pre_qkv; a.pre_att = c->pre_att; a.pre_hid = c->pre_hid; a.pre_rows = pio_context::kPrefillRows;
 }
 
-// launch(stream) captured on the handle's capture stream and instantiated -> *exec.  what: the decode's name in the error message.
-extern "C++" {
-template <class F>
-static int capture_exec(pio_context* c, F launch, const char* what, hipGraphExec_t* exec) {
-  hipGraph_t graph = nullptr;
-  HIP_OK(hipStreamBeginCapture(c->capture_stream, hipStreamCaptureModeThreadLocal));
-  hipError_t le = launch(c->capture_stream);
-  hipError_t ce = hipStreamEndCapture(c->capture_stream, &graph);
-  if (le != hipSuccess) {
-    if (graph) (void)hipGraphDestroy(graph);
-    return fail(PIO_ERR_HIP, std::string(what) + " capture: " + hipGetErrorString(le));
-  }
-  HIP_OK(ce);
-  const hipError_t ie = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  HIP_OK(ie);
+// What pio_decode_greedy and pio_decode_greedy_stop (`who` in the messages) do before their first decode launch: the checks, then *a and
+// on `s` the prefixes and the tickets.  null_arg: a required pointer is missing; bad_stop: what is wrong with the _stop form's own arguments.
+static int greedy_begin(pio_context* c, const char* who, bool null_arg, const char* bad_stop, const float* prefix, int N, int steps,
+                        bool logprob, hipStream_t s, DecoderArgs* a) {
+  const std::string w(who);
+  if (null_arg) return fail(PIO_ERR_INVALID_ARG, w + ": null argument");
+  if (!c->has_dec || !c->has_clip_project) return fail(PIO_ERR_NOT_READY, w + ": decoder weights (with clip_project) not loaded");
+  if (N < 1 || N > c->cfg.max_prefixes) return fail(PIO_ERR_CAPACITY, w + ": N above max_prefixes");
+  if (logprob && N > 64) return fail(PIO_ERR_CAPACITY, w + ": log-probabilities are built for <= 64 prefixes per call");
+  if (steps < 1 || steps > c->cfg.max_steps || steps > 64) return fail(PIO_ERR_CAPACITY, w + ": steps above max_steps");
+  if (bad_stop) return fail(PIO_ERR_INVALID_ARG, w + ": " + bad_stop);
+  HIP_OK(hipSetDevice(c->cfg.device));
+  *a = lm_args(c, N, steps, 0, logprob);
+  HIP_OK(hipMemcpyAsync(c->prefix_buf, prefix, (size_t)N * c->cfg.prefix_size * 4, hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));   // tickets start at zero whatever happened before
   return PIO_OK;
 }
-}  // extern "C++"
 
 int pio_decode_greedy(pio_handle c, const float* prefix, int32_t N, int32_t steps, int32_t* ids, float* logprob,
                       pio_stream stream) {
-  if (!c || !prefix || !ids) return fail(PIO_ERR_INVALID_ARG, "pio_decode_greedy: null argument");
-  if (!c->has_dec || !c->has_clip_project) return fail(PIO_ERR_NOT_READY, "pio_decode_greedy: decoder weights (with clip_project) not loaded");
-  if (N < 1 || N > c->cfg.max_prefixes) return fail(PIO_ERR_CAPACITY, "pio_decode_greedy: N above max_prefixes");
-  if (logprob && N > 64) return fail(PIO_ERR_CAPACITY, "pio_decode_greedy: log-probabilities are built for <= 64 prefixes per call");
-  if (steps < 1 || steps > c->cfg.max_steps || steps > 64) return fail(PIO_ERR_CAPACITY, "pio_decode_greedy: steps above max_steps");
-  HIP_OK(hipSetDevice(c->cfg.device));
   hipStream_t s = (hipStream_t)stream;
-  const int E = c->cfg.dec_embd, PS = c->cfg.prefix_size;
-  const DecoderArgs a = lm_args(c, N, steps, 0, logprob != nullptr);
-  HIP_OK(hipMemcpyAsync(c->prefix_buf, prefix, (size_t)N * PS * 4, hipMemcpyDeviceToDevice, s));
-  HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));   // tickets start at zero whatever happened before
+  DecoderArgs a;
+  int rc;
+  if ((rc = greedy_begin(c, "pio_decode_greedy", !c || !prefix || !ids, nullptr, prefix, N, steps, logprob != nullptr, s, &a))) return rc;
+  const int E = c->cfg.dec_embd;
   // algorithmic work of a KV-cached decode: per token 4 layers x 12 E^2 MACs + the tied LM head;
   // bytes = every fp32 weight read once per step
   const double layer_params = (double)c->cfg.dec_layers * 12.0 * E * E, head_params = (double)c->cfg.dec_vocab * E;
@@ -1627,19 +1654,13 @@ int pio_decode_greedy(pio_handle c, const float* prefix, int32_t N, int32_t step
   // bytes the path streams per step: the layers in fp32; the head in fp16 when ids only are wanted (fp16 filter,
   // plus a handful of fp32 rows for the exact re-evaluation), in fp32 when log-probabilities are
   const double dec_bytes = steps * (4.0 * layer_params + (logprob ? 4.0 : 2.0) * head_params);
-  if (c->use_graph) {
-    const GraphKey key{N, steps, logprob ? 1 : 0};
-    auto it = c->graphs.find(key);
-    if (it == c->graphs.end()) {
-      hipGraphExec_t exec = nullptr;
-      int rc = capture_exec(c, [&](hipStream_t cs) { return launch_decode_greedy(a, cs); }, "decode", &exec);
-      if (rc) return rc;
-      it = c->graphs.emplace(key, exec).first;
-    }
-    PROF(c, PIO_PROF_DECODE, dec_flops, dec_bytes, s, hipGraphLaunch(it->second, s));
-  } else {
-    PROF(c, PIO_PROF_DECODE, dec_flops, dec_bytes, s, launch_decode_greedy(a, s));
-  }
+  const auto launch = [&](hipStream_t cs) { return launch_decode_greedy(a, cs); };
+  DecodeKey key{GREEDY, N, 0, steps};
+  key.lp = logprob ? 1 : 0;
+  GraphEntry* g;
+  if ((rc = c->greedy_graphs.get(c->use_graph, key, 1, &g))) return rc;
+  if ((rc = graph_capture(c->capture_stream, g, 0, launch, "decode"))) return rc;
+  PROF(c, PIO_PROF_DECODE, dec_flops, dec_bytes, s, graph_or_eager(g, 0, launch, s));
   HIP_OK(hipMemcpyAsync(ids, c->ids_buf, (size_t)N * steps * 4, hipMemcpyDeviceToDevice, s));
   if (logprob) HIP_OK(hipMemcpyAsync(logprob, c->logprob_buf, (size_t)N * steps * 4, hipMemcpyDeviceToDevice, s));
   return PIO_OK;
@@ -1766,58 +1787,6 @@ int pio_beam_select(pio_handle c, const float* logp, const float* scores, const 
   return PIO_OK;
 }
 
-// The device hard prompt and the ragged decode are referenced weakly: the host-only AddressSanitizer build of this file
-// (tests/hipstub) links it against stubs of the launchers it has always had, without the kernels; there these entry points report
-// PIO_ERR_NOT_READY.  The library itself always defines them (viecap.hip, decoder.hip).
-extern "C++" {
-namespace pio {
-hipError_t launch_compose_prompts(const ComposeArgs& a, hipStream_t s) __attribute__((weak));
-hipError_t launch_build_prompt_ragged(const float* cont, const int32_t* tokens, const int32_t* lt, const float* wte, int N, int Lc, int Ltmax,
-                                      int E, int V, int soft_first, float* prompt, int32_t* plen, hipStream_t s) __attribute__((weak));
-hipError_t launch_decode_prompted_ragged(const DecoderArgs& a, const float* prompt, int Pmax, const int32_t* plen, int split, hipStream_t s)
-    __attribute__((weak));
-hipError_t launch_lm_beam_search(const DecoderArgs& a, const BeamArgs& b, hipStream_t s) __attribute__((weak));
-// stop_at_eos: the segment launchers (decoder.hip) and the stop bookkeeping (dec_stop.hip)
-hipError_t launch_decode_greedy_segment(const DecoderArgs& a, int s0, int s1, hipStream_t s) __attribute__((weak));
-hipError_t launch_decode_prompted_segment(const DecoderArgs& a, const float* prompt, int P, int s0, int s1, hipStream_t s) __attribute__((weak));
-hipError_t launch_dec_stop_scan(const int32_t* ids, int N, int steps, int s0, int s1, int stop0, int stop1, int32_t* first, int32_t* live,
-                                hipStream_t s) __attribute__((weak));
-hipError_t launch_dec_stop_pad(const int32_t* ids, const int32_t* first, int N, int steps, int32_t* out, hipStream_t s) __attribute__((weak));
-}  // namespace pio
-}  // extern "C++"
-
-// Launch a prompted decode through the handle's graph cache: captured on first use of `key`, a small LRU (see pgraphs).
-extern "C++" {
-template <class F>
-static int launch_prompted_graph(pio_context* c, const pio_context::PKey& key, F launch, hipStream_t s) {
-  auto it = c->pgraphs.find(key);
-  if (it == c->pgraphs.end()) {
-    hipGraphExec_t exec = nullptr;
-    int rc = capture_exec(c, launch, "prompted decode", &exec);
-    if (rc) return rc;
-    if (c->pgraphs.size() >= pio_context::kMaxPGraphs) {       // evict the least recently used graph
-      auto old = c->pgraphs.begin();
-      for (auto jt = c->pgraphs.begin(); jt != c->pgraphs.end(); ++jt)
-        if (jt->second.last_use < old->second.last_use) old = jt;
-      // it may still be running where it was last launched: wait for the event recorded behind that launch (an event outlives the
-      // caller's stream; round 4 synchronised the stored stream handle, which a caller may have destroyed since -- the error then
-      // left the new exec leaked and the dead entry in place for every later decode).  Whatever the wait says, the entry goes.
-      if (old->second.done) { (void)hipEventSynchronize(old->second.done); (void)hipEventDestroy(old->second.done); }
-      (void)hipGraphExecDestroy(old->second.exec);
-      c->pgraphs.erase(old);
-    }
-    hipEvent_t done = nullptr;
-    const hipError_t ee = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-    if (ee != hipSuccess) { (void)hipGraphExecDestroy(exec); HIP_OK(ee); }
-    it = c->pgraphs.emplace(key, pio_context::PGraph{exec, 0, done}).first;
-  }
-  it->second.last_use = ++c->pgraph_clock;
-  HIP_OK(hipGraphLaunch(it->second.exec, s));
-  HIP_OK(hipEventRecord(it->second.done, s));
-  return PIO_OK;
-}
-}  // extern "C++"
-
 // prompt buffer and batched-prefill workspace of the prompted decodes, allocated on first use
 static int prompted_workspaces(pio_context* c, bool prefill) {
   const int E = c->cfg.dec_embd;
@@ -1836,41 +1805,56 @@ static int prompted_workspaces(pio_context* c, bool prefill) {
   return PIO_OK;
 }
 
+// A single-graph prompted decode (`key`, its launches in launch(stream)) through the prompted cache, and behind it the event eviction waits on.
+extern "C++" {
+template <class F>
+static int launch_prompted(pio_context* c, const DecodeKey& key, F launch, hipStream_t s) {
+  GraphEntry* g;
+  int rc;
+  if ((rc = c->prompted_graphs.get(c->use_graph, key, 1, &g))) return rc;
+  if ((rc = graph_launch(c->capture_stream, g, 0, launch, "prompted decode", s))) return rc;
+  return graph_done(g, s);
+}
+}  // extern "C++"
+
+// What pio_viecap_decode and pio_viecap_decode_stop (`who` in the messages) do before their first decode launch: the checks, then on `s`
+// the prompt [N][*P][E] in prompt_buf and the tickets, and *a.  null_arg / bad_stop as in greedy_begin.
+static int viecap_begin(pio_context* c, const char* who, bool null_arg, const char* bad_stop, const float* cont, const int32_t* tokens, int N,
+                        int Lt, int soft_first, int steps, hipStream_t s, DecoderArgs* a, int* P) {
+  const std::string w(who);
+  if (null_arg || (Lt > 0 && !tokens)) return fail(PIO_ERR_INVALID_ARG, w + ": null argument");
+  if (!cont && Lt < 1) return fail(PIO_ERR_INVALID_ARG, w + ": neither a soft prompt nor prompt tokens");
+  if (!c->has_dec || (cont && !c->has_map)) return fail(PIO_ERR_NOT_READY, w + ": language model / mapping network not loaded");
+  if (N < 1 || N > c->cfg.max_prefixes) return fail(PIO_ERR_CAPACITY, w + ": N above max_prefixes");
+  const int Lc = cont ? c->map_Lc : 0;       // cont == NULL: only_hard_prompt (entrypoint.py:130-131), the word embeddings alone
+  *P = Lc + Lt;
+  if (Lt < 0 || steps < 1 || steps > 64 || *P + steps - 1 > c->cfg.max_steps)
+    return fail(PIO_ERR_CAPACITY, w + ": prompt + generated positions above max_steps");
+  if (bad_stop) return fail(PIO_ERR_INVALID_ARG, w + ": " + bad_stop);
+  HIP_OK(hipSetDevice(c->cfg.device));
+  int rc;
+  if ((rc = prompted_workspaces(c, c->batched_prefill))) return rc;
+  if (Lt > 0) HIP_OK(hipMemcpyAsync(c->tok_buf, tokens, (size_t)N * Lt * 4, hipMemcpyDeviceToDevice, s));
+  HIP_OK(launch_build_prompt(cont, c->tok_buf, c->wte, N, Lc, Lt, c->cfg.dec_embd, c->cfg.dec_vocab, soft_first, c->prompt_buf, s));
+  *a = lm_args(c, N, steps, *P - 1);
+  if (c->batched_prefill) with_prefill(*a, c);
+  HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
+  return PIO_OK;
+}
+
 int pio_viecap_decode(pio_handle c, const float* cont, const int32_t* tokens, int32_t N, int32_t Lt, int32_t soft_first,
                       int32_t steps, int32_t* ids, pio_stream stream) {
-  if (!c || !ids || (Lt > 0 && !tokens)) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode: null argument");
-  if (!cont && Lt < 1) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode: neither a soft prompt nor prompt tokens");
-  if (!c->has_dec || (cont && !c->has_map)) return fail(PIO_ERR_NOT_READY, "pio_viecap_decode: language model / mapping network not loaded");
-  if (N < 1 || N > c->cfg.max_prefixes) return fail(PIO_ERR_CAPACITY, "pio_viecap_decode: N above max_prefixes");
-  const int Lc = cont ? c->map_Lc : 0;       // cont == NULL: only_hard_prompt (entrypoint.py:130-131), the word embeddings alone
-  const int P = Lc + Lt;
-  if (Lt < 0 || steps < 1 || steps > 64 || P + steps - 1 > c->cfg.max_steps)
-    return fail(PIO_ERR_CAPACITY, "pio_viecap_decode: prompt + generated positions above max_steps");
-  HIP_OK(hipSetDevice(c->cfg.device));
   hipStream_t s = (hipStream_t)stream;
-  const int E = c->cfg.dec_embd;
-  int rc;
-  const bool batched_prefill = c->batched_prefill;
-  if ((rc = prompted_workspaces(c, batched_prefill))) return rc;
-  if (Lt > 0) HIP_OK(hipMemcpyAsync(c->tok_buf, tokens, (size_t)N * Lt * 4, hipMemcpyDeviceToDevice, s));
-  HIP_OK(launch_build_prompt(cont, c->tok_buf, c->wte, N, Lc, Lt, E, c->cfg.dec_vocab, soft_first, c->prompt_buf, s));
-  DecoderArgs a = lm_args(c, N, steps, P - 1);
-  if (batched_prefill) with_prefill(a, c);
-  HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
-  if (c->use_graph) {
-    int rc2 = launch_prompted_graph(c, pio_context::PKey{pio_context::PROMPTED, N, P, steps},
-                                    [&](hipStream_t cs) { return launch_decode_prompted(a, c->prompt_buf, P, cs); }, s);
-    if (rc2) return rc2;
-  } else {
-    HIP_OK(launch_decode_prompted(a, c->prompt_buf, P, s));
-  }
+  DecoderArgs a;
+  int rc, P;
+  if ((rc = viecap_begin(c, "pio_viecap_decode", !c || !ids, nullptr, cont, tokens, N, Lt, soft_first, steps, s, &a, &P))) return rc;
+  if ((rc = launch_prompted(c, DecodeKey{PROMPTED, N, P, steps}, [&](hipStream_t cs) { return launch_decode_prompted(a, c->prompt_buf, P, cs); }, s)))
+    return rc;
   HIP_OK(hipMemcpyAsync(ids, c->ids_buf, (size_t)N * steps * 4, hipMemcpyDeviceToDevice, s));
   return PIO_OK;
 }
 
 // ---- stop_at_eos: a synchronous greedy decode in segments of `seg` steps that ends once every row has emitted a stop id ----
-#define PIO_STOP_LINKED (launch_decode_greedy_segment && launch_decode_prompted_segment && launch_dec_stop_scan && launch_dec_stop_pad)
-
 static int stop_state(pio_context* c) {
   int rc;
   if (!c->stop_first) {
@@ -1888,44 +1872,21 @@ static int stop_state(pio_context* c) {
 // Then canon(ids) -> ids.  *steps_run = steps the device was given.
 extern "C++" {
 template <class F>
-static int run_stop_decode(pio_context* c, const pio_context::SKey& key, const DecoderArgs& a, F segment, int32_t* ids, int32_t* steps_run,
+static int run_stop_decode(pio_context* c, const DecodeKey& key, const DecoderArgs& a, F segment, int32_t* ids, int32_t* steps_run,
                            hipStream_t s) {
   const int N = key.N, steps = key.steps, seg = key.seg;
-  auto launch = [&](int s0, int s1, hipStream_t cs) -> hipError_t {
-    const hipError_t e = segment(s0, s1, cs);
-    return e != hipSuccess ? e : launch_dec_stop_scan(a.ids, N, steps, s0, s1, key.stop0, key.stop1, c->stop_first, c->stop_live, cs);
-  };
-  pio_context::SDecode* d = nullptr;
-  if (c->use_graph) {
-    auto it = c->sgraphs.find(key);
-    if (it == c->sgraphs.end()) {
-      if (c->sgraphs.size() >= pio_context::kMaxSDecodes) {     // evict the least recently used decode, all its segments (see launch_prompted_graph)
-        auto old = c->sgraphs.begin();
-        for (auto jt = c->sgraphs.begin(); jt != c->sgraphs.end(); ++jt)
-          if (jt->second.last_use < old->second.last_use) old = jt;
-        if (old->second.done) { (void)hipEventSynchronize(old->second.done); (void)hipEventDestroy(old->second.done); }
-        for (hipGraphExec_t e : old->second.segs) if (e) (void)hipGraphExecDestroy(e);
-        c->sgraphs.erase(old);
-      }
-      hipEvent_t done = nullptr;
-      HIP_OK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-      it = c->sgraphs.emplace(key, pio_context::SDecode{std::vector<hipGraphExec_t>((size_t)((steps + seg - 1) / seg), nullptr), 0, done}).first;
-    }
-    d = &it->second;
-    d->last_use = ++c->pgraph_clock;
-  }
+  int rc;
+  if ((rc = stop_state(c))) return rc;
+  GraphEntry* g;
+  if ((rc = c->stop_graphs.get(c->use_graph, key, (size_t)((steps + seg - 1) / seg), &g))) return rc;
   int run = 0;
   for (int k = 0, s0 = 0; s0 < steps; ++k, s0 += seg) {
     const int s1 = s0 + seg < steps ? s0 + seg : steps;
-    if (d) {
-      if (!d->segs[k]) {
-        int rc = capture_exec(c, [&](hipStream_t cs) { return launch(s0, s1, cs); }, "segment decode", &d->segs[k]);
-        if (rc) return rc;
-      }
-      HIP_OK(hipGraphLaunch(d->segs[k], s));
-    } else {
-      HIP_OK(launch(s0, s1, s));
-    }
+    const auto launch = [&](hipStream_t cs) -> hipError_t {
+      const hipError_t e = segment(s0, s1, cs);
+      return e != hipSuccess ? e : launch_dec_stop_scan(a.ids, N, steps, s0, s1, key.stop0, key.stop1, c->stop_first, c->stop_live, cs);
+    };
+    if ((rc = graph_launch(c->capture_stream, g, (size_t)k, launch, "segment decode", s))) return rc;
     run = s1;
     if (s1 == steps) break;
     HIP_OK(hipMemcpyAsync(c->stop_live_host, c->stop_live, sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1934,7 +1895,7 @@ static int run_stop_decode(pio_context* c, const pio_context::SKey& key, const D
     if (*c->stop_live_host <= 0) break;
   }
   HIP_OK(launch_dec_stop_pad(a.ids, c->stop_first, N, steps, ids, s));
-  if (d) HIP_OK(hipEventRecord(d->done, s));
+  if ((rc = graph_done(g, s))) return rc;
   *steps_run = run;
   return PIO_OK;
 }
@@ -1942,48 +1903,29 @@ static int run_stop_decode(pio_context* c, const pio_context::SKey& key, const D
 
 int pio_decode_greedy_stop(pio_handle c, const float* prefix, int32_t N, int32_t steps, int32_t eos_id, int32_t seg, int32_t* ids,
                            int32_t* steps_run_host, pio_stream stream) {
-  if (!c || !prefix || !ids || !steps_run_host) return fail(PIO_ERR_INVALID_ARG, "pio_decode_greedy_stop: null argument");
-  if (!c->has_dec || !c->has_clip_project) return fail(PIO_ERR_NOT_READY, "pio_decode_greedy_stop: decoder weights (with clip_project) not loaded");
-  if (N < 1 || N > c->cfg.max_prefixes) return fail(PIO_ERR_CAPACITY, "pio_decode_greedy_stop: N above max_prefixes");
-  if (steps < 1 || steps > c->cfg.max_steps || steps > 64) return fail(PIO_ERR_CAPACITY, "pio_decode_greedy_stop: steps above max_steps");
-  if (seg < 1 || eos_id < 0) return fail(PIO_ERR_INVALID_ARG, "pio_decode_greedy_stop: seg >= 1 and a stop id >= 0");
-  if (!PIO_STOP_LINKED) return fail(PIO_ERR_NOT_READY, "pio_decode_greedy_stop: built without the kernels");
-  HIP_OK(hipSetDevice(c->cfg.device));
   hipStream_t s = (hipStream_t)stream;
+  DecoderArgs a;
   int rc;
-  if ((rc = stop_state(c))) return rc;
-  const DecoderArgs a = lm_args(c, N, steps, 0, false);
-  HIP_OK(hipMemcpyAsync(c->prefix_buf, prefix, (size_t)N * c->cfg.prefix_size * 4, hipMemcpyDeviceToDevice, s));
-  HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
-  const pio_context::SKey key{pio_context::STOP_GREEDY, N, 0, steps, seg < steps ? seg : steps, eos_id, -1};
+  if ((rc = greedy_begin(c, "pio_decode_greedy_stop", !c || !prefix || !ids || !steps_run_host,
+                         (seg < 1 || eos_id < 0) ? "seg >= 1 and a stop id >= 0" : nullptr, prefix, N, steps, false, s, &a)))
+    return rc;
+  DecodeKey key{STOP_GREEDY, N, 0, steps};
+  key.seg = seg < steps ? seg : steps; key.stop0 = eos_id; key.stop1 = -1;
   return run_stop_decode(c, key, a, [&](int s0, int s1, hipStream_t cs) { return launch_decode_greedy_segment(a, s0, s1, cs); }, ids,
                          steps_run_host, s);
 }
 
 int pio_viecap_decode_stop(pio_handle c, const float* cont, const int32_t* tokens, int32_t N, int32_t Lt, int32_t soft_first, int32_t steps,
                            int32_t eos0, int32_t eos1, int32_t seg, int32_t* ids, int32_t* steps_run_host, pio_stream stream) {
-  if (!c || !ids || !steps_run_host || (Lt > 0 && !tokens)) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode_stop: null argument");
-  if (!cont && Lt < 1) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode_stop: neither a soft prompt nor prompt tokens");
-  if (!c->has_dec || (cont && !c->has_map)) return fail(PIO_ERR_NOT_READY, "pio_viecap_decode_stop: language model / mapping network not loaded");
-  if (N < 1 || N > c->cfg.max_prefixes) return fail(PIO_ERR_CAPACITY, "pio_viecap_decode_stop: N above max_prefixes");
-  const int Lc = cont ? c->map_Lc : 0;
-  const int P = Lc + Lt;
-  if (Lt < 0 || steps < 1 || steps > 64 || P + steps - 1 > c->cfg.max_steps)
-    return fail(PIO_ERR_CAPACITY, "pio_viecap_decode_stop: prompt + generated positions above max_steps");
-  if (seg < 1 || eos0 < 0) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode_stop: seg >= 1 and a first stop id >= 0 (eos1 < 0: none)");
-  if (!PIO_STOP_LINKED) return fail(PIO_ERR_NOT_READY, "pio_viecap_decode_stop: built without the kernels");
-  HIP_OK(hipSetDevice(c->cfg.device));
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  const bool batched_prefill = c->batched_prefill;
-  if ((rc = prompted_workspaces(c, batched_prefill))) return rc;
-  if ((rc = stop_state(c))) return rc;
-  if (Lt > 0) HIP_OK(hipMemcpyAsync(c->tok_buf, tokens, (size_t)N * Lt * 4, hipMemcpyDeviceToDevice, s));
-  HIP_OK(launch_build_prompt(cont, c->tok_buf, c->wte, N, Lc, Lt, c->cfg.dec_embd, c->cfg.dec_vocab, soft_first, c->prompt_buf, s));
-  DecoderArgs a = lm_args(c, N, steps, P - 1);
-  if (batched_prefill) with_prefill(a, c);
-  HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
-  const pio_context::SKey key{pio_context::STOP_PROMPTED, N, P, steps, seg < steps ? seg : steps, eos0, eos1 < 0 ? -1 : eos1};
+  DecoderArgs a;
+  int rc, P;
+  if ((rc = viecap_begin(c, "pio_viecap_decode_stop", !c || !ids || !steps_run_host,
+                         (seg < 1 || eos0 < 0) ? "seg >= 1 and a first stop id >= 0 (eos1 < 0: none)" : nullptr, cont, tokens, N, Lt, soft_first,
+                         steps, s, &a, &P)))
+    return rc;
+  DecodeKey key{STOP_PROMPTED, N, P, steps};
+  key.seg = seg < steps ? seg : steps; key.stop0 = eos0; key.stop1 = eos1 < 0 ? -1 : eos1;
   return run_stop_decode(c, key, a, [&](int s0, int s1, hipStream_t cs) { return launch_decode_prompted_segment(a, c->prompt_buf, P, s0, s1, cs); },
                          ids, steps_run_host, s);
 }
@@ -1997,7 +1939,6 @@ int pio_viecap_compose_prompts(pio_handle c, const float* probs, int32_t N, int3
   if (N < 1 || K < 1 || Lmax < 1 || head_len < 0 || empty_len < 0 || head_off < 0 || empty_off < 0)
     return fail(PIO_ERR_INVALID_ARG, "pio_viecap_compose_prompts: bad shape");
   if (top_k < 1 || top_k > 8) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_compose_prompts: top_k must be 1..8");
-  if (!launch_compose_prompts) return fail(PIO_ERR_NOT_READY, "pio_viecap_compose_prompts: built without the kernels");
   HIP_OK(hipSetDevice(c->cfg.device));
   ComposeArgs a;
   a.probs = probs; a.N = N; a.K = K; a.frag_ids = frag_ids; a.frag_off = frag_off; a.frag_len = frag_len;
@@ -2016,7 +1957,6 @@ int pio_viecap_decode_ragged(pio_handle c, const float* cont, const int32_t* tok
   if (!c->has_dec || (cont && !owner->has_map)) return fail(PIO_ERR_NOT_READY, "pio_viecap_decode_ragged: language model / mapping network not loaded");
   if (N < 1 || N > c->cfg.max_prefixes || N > 128) return fail(PIO_ERR_CAPACITY, "pio_viecap_decode_ragged: N above min(max_prefixes, 128)");
   if (c->lm_tail) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_decode_ragged: the ticketed LM-head tail (PIO_LM_TAIL=1) has no ragged form");
-  if (!launch_build_prompt_ragged || !launch_decode_prompted_ragged) return fail(PIO_ERR_NOT_READY, "pio_viecap_decode_ragged: built without the kernels");
   const int Lc = cont ? owner->map_Lc : 0;
   const int Pmax = Lc + Ltmax;
   if (Ltmax < 0 || steps < 1 || steps > 64 || Pmax + steps - 1 > c->cfg.max_steps)
@@ -2035,13 +1975,9 @@ int pio_viecap_decode_ragged(pio_handle c, const float* cont, const int32_t* tok
   HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
   const int32_t* plen = c->plen_buf;
   const int split = c->batched_prefill ? 16 : 256;      // the prompt lengths pio_viecap_decode prefills on one row group (decoder.hip)
-  if (c->use_graph) {
-    if ((rc = launch_prompted_graph(c, pio_context::PKey{pio_context::RAGGED, N, Pmax, steps},
-                                    [&](hipStream_t cs) { return launch_decode_prompted_ragged(a, c->prompt_buf, Pmax, plen, split, cs); }, s)))
-      return rc;
-  } else {
-    HIP_OK(launch_decode_prompted_ragged(a, c->prompt_buf, Pmax, plen, split, s));
-  }
+  if ((rc = launch_prompted(c, DecodeKey{RAGGED, N, Pmax, steps},
+                            [&](hipStream_t cs) { return launch_decode_prompted_ragged(a, c->prompt_buf, Pmax, plen, split, cs); }, s)))
+    return rc;
   HIP_OK(hipMemcpyAsync(ids, c->ids_buf, (size_t)N * steps * 4, hipMemcpyDeviceToDevice, s));
   return PIO_OK;
 }
@@ -2054,7 +1990,6 @@ int pio_viecap_build_prompt_ragged(pio_handle c, const float* cont, const int32_
   if (!c->has_dec || (cont && !owner->has_map))
     return fail(PIO_ERR_NOT_READY, "pio_viecap_build_prompt_ragged: language model / mapping network not loaded");
   if (N < 1 || Ltmax < 0) return fail(PIO_ERR_INVALID_ARG, "pio_viecap_build_prompt_ragged: bad shape");
-  if (!launch_build_prompt_ragged) return fail(PIO_ERR_NOT_READY, "pio_viecap_build_prompt_ragged: built without the kernels");
   HIP_OK(hipSetDevice(c->cfg.device));
   HIP_OK(launch_build_prompt_ragged(cont, tokens, Ltmax > 0 ? lens : nullptr, c->wte, N, cont ? owner->map_Lc : 0, Ltmax, c->cfg.dec_embd,
                                     c->cfg.dec_vocab, soft_first, prompt, plen, (hipStream_t)stream));
@@ -2065,7 +2000,6 @@ int pio_lm_beam_search(pio_handle c, const float* embeds, const int32_t* plen, i
                        int32_t eos1, int32_t* ids, int32_t* lens, float* scores, pio_stream stream) {
   if (!c || !embeds || !ids || !lens || !scores) return fail(PIO_ERR_INVALID_ARG, "pio_lm_beam_search: null argument");
   if (!c->has_dec) return fail(PIO_ERR_NOT_READY, "pio_lm_beam_search: language model not loaded");
-  if (!launch_lm_beam_search) return fail(PIO_ERR_NOT_READY, "pio_lm_beam_search: built without the kernels");
   if (W < 1 || W > 8) return fail(PIO_ERR_INVALID_ARG, "pio_lm_beam_search: beam width must be 1..8");
   const int cap = c->cfg.max_prefixes < 128 ? c->cfg.max_prefixes : 128;
   if (N < 1 || N * W > cap) return fail(PIO_ERR_CAPACITY, "pio_lm_beam_search: N * W above min(max_prefixes, 128) rows");
@@ -2095,34 +2029,18 @@ int pio_lm_beam_search(pio_handle c, const float* embeds, const int32_t* plen, i
   b.prow = c->bs_i; b.pimg = c->bs_i + Rc; b.tok = c->bs_i + 2 * Rc; b.stopped = c->bs_i + 3 * Rc;
   b.tab = c->bs_i + 6 * Rc; b.hist = c->bs_i + (size_t)6 * Rc + (size_t)Rc * S;
   HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
-  if (c->use_graph) {
-    const pio_context::PKey key{pio_context::BEAM, N, Pmax, steps, W, plen ? 1 : 0, eos0, eos1};
-    if ((rc = launch_prompted_graph(c, key, [&](hipStream_t cs) { return launch_lm_beam_search(a, b, cs); }, s))) return rc;
-  } else {
-    HIP_OK(launch_lm_beam_search(a, b, s));
-  }
+  DecodeKey key{BEAM, N, Pmax, steps};
+  key.W = W; key.has_plen = plen ? 1 : 0; key.eos0 = eos0; key.eos1 = eos1;
+  if ((rc = launch_prompted(c, key, [&](hipStream_t cs) { return launch_lm_beam_search(a, b, cs); }, s))) return rc;
   HIP_OK(hipMemcpyAsync(ids, b.ids, (size_t)R * steps * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   HIP_OK(hipMemcpyAsync(lens, b.out_lens, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   HIP_OK(hipMemcpyAsync(scores, b.out_scores, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, s));
   return PIO_OK;
 }
 
-// The sampler and the sampling loop are referenced weakly for the same reason as the launchers above (sample.hip, decoder.hip).
-extern "C++" {
-namespace pio {
-hipError_t launch_nucleus_sample(const SampleArgs& a, hipStream_t s) __attribute__((weak));
-hipError_t launch_philox_uniforms(uint64_t seed, int N, int steps, float* u, hipStream_t s) __attribute__((weak));
-hipError_t launch_lm_sample(const DecoderArgs& a, const float* prompt, int P, float temperature, float top_p, int stop_id,
-                            const float* uniforms, int32_t* active, float* stats, int32_t* lens, hipStream_t s) __attribute__((weak));
-hipError_t launch_clipcap_mapping(const float* x, int N, int C, int H, int Nout, const float* w1, const float* b1, const float* w2,
-                                  const float* b2, const float* zeros, float* hid, float* out, hipStream_t s) __attribute__((weak));
-}  // namespace pio
-}  // extern "C++"
-
 int pio_clipcap_mapping(pio_handle c, const float* feats, int32_t N, int32_t normalize, float* out, pio_stream stream) {
   if (!c || !feats || !out) return fail(PIO_ERR_INVALID_ARG, "pio_clipcap_mapping: null argument");
   if (!c->has_ccmap) return fail(PIO_ERR_NOT_READY, "pio_clipcap_mapping: ClipCap mapper (clip_project.model.0 / .2) not loaded");
-  if (!launch_clipcap_mapping) return fail(PIO_ERR_NOT_READY, "pio_clipcap_mapping: built without the kernels");
   if (N < 1 || N > c->cfg.max_prefixes || N > 128) return fail(PIO_ERR_CAPACITY, "pio_clipcap_mapping: N above min(max_prefixes, 128)");
   HIP_OK(hipSetDevice(c->cfg.device));
   hipStream_t s = (hipStream_t)stream;
@@ -2141,7 +2059,6 @@ int pio_clipcap_prefix_length(pio_handle c) { return (c && c->has_ccmap) ? c->cc
 int pio_nucleus_sample(pio_handle c, const float* scores, int32_t N, float temperature, float top_p, const float* uniforms, int32_t stop_id,
                        int32_t* active, int32_t* tokens, int32_t* kept, pio_stream stream) {
   if (!c || !scores || !uniforms || !active || !tokens) return fail(PIO_ERR_INVALID_ARG, "pio_nucleus_sample: null argument");
-  if (!launch_nucleus_sample) return fail(PIO_ERR_NOT_READY, "pio_nucleus_sample: built without the kernels");
   if (N < 1 || c->cfg.dec_vocab < 1) return fail(PIO_ERR_INVALID_ARG, "pio_nucleus_sample: bad shape");
   HIP_OK(hipSetDevice(c->cfg.device));
   SampleArgs a;
@@ -2155,7 +2072,6 @@ int pio_lm_sample(pio_handle c, const float* embeds, int32_t N, int32_t P, int32
                   uint64_t seed, const float* uniforms, int32_t* ids, int32_t* lens, pio_stream stream) {
   if (!c || !embeds || !ids || !lens) return fail(PIO_ERR_INVALID_ARG, "pio_lm_sample: null argument");
   if (!c->has_dec) return fail(PIO_ERR_NOT_READY, "pio_lm_sample: language model not loaded");
-  if (!launch_lm_sample || !launch_philox_uniforms) return fail(PIO_ERR_NOT_READY, "pio_lm_sample: built without the kernels");
   const int cap = c->cfg.max_prefixes < 128 ? c->cfg.max_prefixes : 128;
   if (N < 1 || P < 1 || steps < 1) return fail(PIO_ERR_INVALID_ARG, "pio_lm_sample: N, P and steps must be positive");
   if (N > cap) return fail(PIO_ERR_CAPACITY, "pio_lm_sample: N above min(max_prefixes, 128)");
@@ -2180,14 +2096,10 @@ int pio_lm_sample(pio_handle c, const float* embeds, int32_t N, int32_t P, int32
   HIP_OK(hipMemsetAsync(c->splitk_cnt, 0, DEC_TICKET_WORDS * sizeof(unsigned), s));
   int32_t *active = c->smp_i, *lens_buf = c->smp_i + cap;
   auto launch = [&](hipStream_t cs) { return launch_lm_sample(a, c->prompt_buf, P, temperature, top_p, stop_id, c->smp_u, active, c->bs_f, lens_buf, cs); };
-  if (c->use_graph) {
-    pio_context::PKey key{pio_context::SAMPLE, N, P, steps};   // temperature, top_p and stop_id are kernel arguments of the graph
-    key.stop_id = stop_id;
-    memcpy(&key.temp_bits, &temperature, 4); memcpy(&key.top_p_bits, &top_p, 4);
-    if ((rc = launch_prompted_graph(c, key, launch, s))) return rc;
-  } else {
-    HIP_OK(launch(s));
-  }
+  DecodeKey key{SAMPLE, N, P, steps};   // temperature, top_p and stop_id are kernel arguments of the graph
+  key.stop_id = stop_id;
+  memcpy(&key.temp_bits, &temperature, 4); memcpy(&key.top_p_bits, &top_p, 4);
+  if ((rc = launch_prompted(c, key, launch, s))) return rc;
   HIP_OK(hipMemcpyAsync(ids, c->ids_buf, (size_t)N * steps * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   HIP_OK(hipMemcpyAsync(lens, lens_buf, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   return PIO_OK;

@@ -1,6 +1,8 @@
 // C ABI test hooks (include/patchioner_hip.h, "Test hooks"): one ViT block kernel, one decoder layer GEMM / attention launch, one beam
 // selection / bookkeeping step / head pass, one bank pass of the memory projection, or one exact-fp32 kernel (GEMM, attention, LayerNorm,
-// pointwise, im2col / scatter, text embed / pool), per call on caller-owned device buffers, for the kernel-by-kernel tests.  A translation unit of its own: api.cpp's host side (tests/test_asan_host.py) does not link the kernels' launchers.
+// pointwise, im2col / scatter, text embed / pool), per call on caller-owned device buffers, for the kernel-by-kernel tests.
+// A translation unit of its own: the host-only AddressSanitizer build (tests/test_asan_host.py) is api.cpp alone against a stub of every
+// launcher that api.cpp calls (tests/hipstub/hip_stub.cpp), and these hooks call launchers that api.cpp does not.
 #include "../../include/patchioner_hip.h"
 
 #include <hip/hip_runtime.h>

@@ -9,8 +9,14 @@
 #include <cstring>
 
 #include "kernels.h"
+#include "resnet.h"
+
+// "fail the next call of X" (asan_loop.cpp): the call returns an error and hands nothing out, the one after it works again
+static bool g_fail_instantiate = false, g_fail_event_create = false;
 
 extern "C" {
+void hip_stub_fail_next_graph_instantiate() { g_fail_instantiate = true; }
+void hip_stub_fail_next_event_create() { g_fail_event_create = true; }
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipDeviceSynchronize() { return hipSuccess; }
@@ -29,14 +35,22 @@ hipError_t hipExtStreamCreateWithCUMask(hipStream_t* s, uint32_t, const uint32_t
 hipError_t hipStreamDestroy(hipStream_t s) { delete (int*)s; return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t s) { if (s) { volatile int v = *(int*)s; (void)v; } return hipSuccess; }   // touches it: use-after-destroy is caught
 hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t) new int(3); return hipSuccess; }
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t) new int(3); return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) {
+  if (g_fail_event_create) { g_fail_event_create = false; return hipErrorOutOfMemory; }
+  *e = (hipEvent_t) new int(3);
+  return hipSuccess;
+}
 hipError_t hipEventDestroy(hipEvent_t e) { delete (int*)e; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { volatile int v = *(int*)e; (void)v; return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t e) { volatile int v = *(int*)e; (void)v; return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
 hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipSuccess; }
 hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t* g) { *g = (hipGraph_t) new int(4); return hipSuccess; }
-hipError_t hipGraphInstantiate(hipGraphExec_t* e, hipGraph_t, hipGraphNode_t*, char*, size_t) { *e = (hipGraphExec_t) new int(5); return hipSuccess; }
+hipError_t hipGraphInstantiate(hipGraphExec_t* e, hipGraph_t, hipGraphNode_t*, char*, size_t) {
+  if (g_fail_instantiate) { g_fail_instantiate = false; return hipErrorOutOfMemory; }
+  *e = (hipGraphExec_t) new int(5);
+  return hipSuccess;
+}
 hipError_t hipGraphDestroy(hipGraph_t g) { delete (int*)g; return hipSuccess; }
 hipError_t hipGraphExecDestroy(hipGraphExec_t e) { delete (int*)e; return hipSuccess; }
 hipError_t hipGraphLaunch(hipGraphExec_t e, hipStream_t) { volatile int v = *(int*)e; (void)v; return hipSuccess; }
@@ -87,4 +101,27 @@ hipError_t launch_sgemm_tn(const float*, int, const float*, int, const float*, f
 hipError_t launch_build_prompt(const float*, const int32_t*, const float*, int, int, int, int, int, int, float*, hipStream_t) { return hipSuccess; }
 hipError_t launch_preprocess(const uint8_t*, const PrepImage*, const int32_t*, uint8_t*, const float*, int, int, int, float*, hipStream_t) { return hipSuccess; }
 hipError_t dec_split_weights(const float*, size_t, void*, float* unscale, hipStream_t) { *unscale = 1.f; return hipSuccess; }
+hipError_t launch_im2col_alpha(int, const float*, const int32_t*, const uint8_t*, int, int, int, int, int, void*, hipStream_t) { return hipSuccess; }
+hipError_t launch_region_masks(const float*, const int32_t*, const double*, const int32_t*, int, int, float, uint8_t*, hipStream_t) { return hipSuccess; }
+hipError_t launch_gather_rows(const float*, const int32_t*, int, int, int, int, int, float*, int32_t*, hipStream_t) { return hipSuccess; }
+hipError_t launch_region_reduce_rows(const float*, const int32_t*, int, int, const float*, const int32_t*, int, float, float*, hipStream_t) { return hipSuccess; }
+hipError_t launch_compose_prompts(const ComposeArgs&, hipStream_t) { return hipSuccess; }
+hipError_t launch_build_prompt_ragged(const float*, const int32_t*, const int32_t*, const float*, int, int, int, int, int, int, float*, int32_t*, hipStream_t) { return hipSuccess; }
+hipError_t launch_decode_prompted_ragged(const DecoderArgs&, const float*, int, const int32_t*, int, hipStream_t) { return hipSuccess; }
+hipError_t launch_lm_beam_search(const DecoderArgs&, const BeamArgs&, hipStream_t) { return hipSuccess; }
+hipError_t launch_decode_greedy_segment(const DecoderArgs&, int, int, hipStream_t) { return hipSuccess; }
+hipError_t launch_decode_prompted_segment(const DecoderArgs&, const float*, int, int, int, hipStream_t) { return hipSuccess; }
+// steers the host's segment loop: a decode whose first stop id is 0 ends after its first segment, every other one runs to its last.  (It
+// "runs" when the launches are captured or made eagerly: a replayed graph leaves the count of the last decode that did.)
+hipError_t launch_dec_stop_scan(const int32_t*, int N, int, int, int, int stop0, int, int32_t*, int32_t* live, hipStream_t) { *live = stop0 == 0 ? 0 : N; return hipSuccess; }
+hipError_t launch_dec_stop_pad(const int32_t*, const int32_t*, int, int, int32_t*, hipStream_t) { return hipSuccess; }
+hipError_t launch_nucleus_sample(const SampleArgs&, hipStream_t) { return hipSuccess; }
+hipError_t launch_philox_uniforms(uint64_t, int, int, float*, hipStream_t) { return hipSuccess; }
+hipError_t launch_lm_sample(const DecoderArgs&, const float*, int, float, float, int, const float*, int32_t*, float*, int32_t*, hipStream_t) { return hipSuccess; }
+hipError_t launch_clipcap_mapping(const float*, int, int, int, int, const float*, const float*, const float*, const float*, const float*, float*, float*, hipStream_t) { return hipSuccess; }
+// the ResNet tower: a heap object that the handle owns between rn_build and rn_destroy
+struct RnNet { int B; };
+int rn_build(const pio_config& cfg, const RnGet&, RnNet** out) { *out = new RnNet{cfg.max_batch}; return PIO_OK; }
+void rn_destroy(RnNet* r) { delete r; }
+int rn_forward(RnNet* r, const float*, int B, float*, hipStream_t) { return B <= r->B ? PIO_OK : PIO_ERR_CAPACITY; }
 }  // namespace pio

@@ -99,8 +99,8 @@ def test_the_check_is_fast_on_thousands_of_entities():
 
 
 def test_the_library_defines_the_device_prompt_launchers():
-    """api.cpp references the launchers of the device hard prompt and of the ragged decode weakly (its host-only AddressSanitizer build links
-    without the kernels); the library itself must define them, with these signatures."""
+    """The library defines the launchers of the device hard prompt and of the ragged decode with the signatures that api.cpp and the host-only
+    AddressSanitizer build's stubs (tests/hipstub/hip_stub.cpp) declare: a changed signature shows here by its mangled name."""
     import ctypes
     import os
     from patchioner_amd import build
